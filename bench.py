@@ -23,6 +23,11 @@ owned cell, including the Courant-number reduction.  Workloads:
 children, RANK / WORLD_SIZE / MASTER_* set; rdycore_amd/launch.py) and relays rank 0's line; under
 torch.distributed.run (WORLD_SIZE already set) it is simply one of the ranks.  State is resident in HBM
 before the timed region.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, conditions and warms the device, times the --steps steps and prints the headline figure with its
+config.  --full adds, after the timed steps, what takes runs of its own: the roofline (kernel-isolated and steady-state
+launch periods, PMC traffic), the fused Euler step, the advance pattern, the halo exchange alone, the cell-order study and
+the CPU baselines.  --dump-outputs DIR writes what the last timed step computed (bench.dump_outputs).
 """
 from __future__ import annotations
 
@@ -47,6 +52,8 @@ LIMITERS = {"minmod": 0, "none": 1, "van_leer": 2}
 ALG_BYTES_PER_CELL_SECOND_ORDER = 176.0 + 16.0 + 24.0
 CPU_FULL_MESH_MAX_CELLS = 12_000_000   # cpu_baseline runs on the benchmark mesh itself up to this size (C3: 10 M cells, ~1 s per RHS on one core)
 KERNEL_SOURCES = ["swe_kernels.h", "swe_device.h", "muscl_kernels.h"]
+DUMP_MAX_ROWS = 1 << 20        # --dump-outputs: rows of F written at most (24 MiB + 8 MiB of row indices)
+DUMP_SEED = 20240229
 HOUSTON_DATA = os.path.join(ROOT, "tests", "golden", "houston")   # the reference's Houston1km fixtures (data files, in the repo)
 
 
@@ -88,9 +95,17 @@ def parse(argv=None):
     p.add_argument("--inject-fault", default="none", choices=["none", "exchange"],
                    help="test hook of the N > 1 self-check: 'exchange' makes the last rank expect a wrong ghost value, so that the run must end "
                         "with the one-line {\"error\": ...} and a non-zero exit code (tests/test_gpu_multirank.py)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-cpu-all-cores", action="store_true", help="skip the all-host-cores CPU figure (the 1-core cpu_baseline stays)")
-    p.add_argument("--no-order-study", action="store_true", help="skip the row-major / Hilbert numbering figures (c3, N = 1 only)")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline figure, measure everything else the line can hold: roofline (kernel-isolated and "
+                        "steady-state launch periods, PMC traffic), the fused Euler step, the advance pattern, the halo exchange "
+                        "alone, the cell-order study and the CPU baselines.  Off: the line holds the headline figure and config only")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write what the last timed step computed on rank 0 to DIR/<name>.npy (float64): rhs = F of the owned cells "
+                        "(a fixed seeded sample of DUMP_MAX_ROWS rows on larger meshes, their indices in rhs_rows), courant = the "
+                        "step's Courant struct (max number, global edge id, global cell id)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip every CPU figure")
+    p.add_argument("--no-cpu-all-cores", action="store_true", help="--full: skip the all-host-cores CPU figure (the 1-core cpu_baseline stays)")
+    p.add_argument("--no-order-study", action="store_true", help="--full: skip the row-major / Hilbert numbering figures (c3, N = 1 only)")
     p.add_argument("--kernel", default=None, choices=["tiled", "cell"], help="kernel variant (default: library default = tiled)")
     p.add_argument("--cpu-sample", default=None, help="nx x ny of the CPU-baseline sample mesh")
     p.add_argument("--launch-timeout", type=float, default=1500.0, help="N > 1 self-launch: give up after this many seconds")
@@ -364,6 +379,28 @@ def load_traffic(workload_key: str, layout_bytes: int, second_order: bool = Fals
     return ent.get("hbm_bytes_per_launch"), src
 
 
+def dump_outputs(out_dir: str, op, f) -> None:
+    """--dump-outputs: F of the last timed step and the Courant struct its launch left, as two builds' outputs can be compared
+    (same arguments = same inputs).  Rows of F beyond DUMP_MAX_ROWS are sampled with a fixed seed, so that two runs on the
+    same mesh write the same rows."""
+    import numpy as np
+    import torch
+    n = f.shape[0]
+    if n > DUMP_MAX_ROWS:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_MAX_ROWS, replace=False))
+        rhs = f[torch.as_tensor(rows, device=f.device)].cpu().numpy()
+    else:
+        rows = np.arange(n)
+        rhs = f.cpu().numpy()
+    op.update_diagnostics()
+    cd = op.get_diagnostics()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "rhs.npy"), np.ascontiguousarray(rhs, dtype=np.float64))
+    np.save(os.path.join(out_dir, "rhs_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "courant.npy"),
+            np.array([cd.max_courant_num, cd.global_edge_id, cd.global_cell_id], dtype=np.float64))
+
+
 def run_rank(args, argv):
     if args.watchdog_seconds > 0:
         import faulthandler
@@ -597,31 +634,10 @@ def run_rank(args, argv):
     else:
         total_cells = max_cells = n_owned
 
-    # ---- dominant kernel: average duration with HIP events on the launch stream (one rhs call = ONE launch)
-    k_iters = max(10, min(args.steps, 50))
-    starts = [torch.cuda.Event(enable_timing=True) for _ in range(k_iters)]
-    ends = [torch.cuda.Event(enable_timing=True) for _ in range(k_iters)]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, op, f)
 
-    def kernel_only():
-        if self_halo is not None:
-            return step()
-        if args.second_order and halo is not None:
-            # the ghost gradients of the last timed step are still in place: the flux launch alone
-            op.apply_phase(0, True, case.dt, u, f, reset_diagnostics=True, gradients_ready=True)
-        else:
-            op.rhs_function(case.dt, u, f)
-
-    for i in range(k_iters):
-        starts[i].record()
-        kernel_only()
-        ends[i].record()
-    torch.cuda.synchronize()
-    kern_all = [s.elapsed_time(e) for s, e in zip(starts, ends)]
-    kern_isolated_ms = float(np.mean(kern_all))
-    # the figure the roofline uses: HIP events around the whole timed region / steps (one RHS = one launch, so this is the
-    # launch-to-launch period including the dispatch gap); with several ranks the region also holds the exchange, so the
-    # individually bracketed launches are used there
-    kern_ms = ev0.elapsed_time(ev1) / args.steps if world == 1 else kern_isolated_ms
+    halo_ms = None
 
     def timed(fn, n, sync_ranks=True, lead=40):
         """ms per call over n back-to-back calls.  `lead` untimed calls go first with no gap before the timed ones: after
@@ -639,101 +655,130 @@ def run_rank(args, argv):
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) / n
 
-    # steady state: the launch-to-launch period of back-to-back launches, median over batches (what a long run sees)
-    periods = []
-    if world == 1:
-        for _ in range(40):
+    # ---- everything beyond the headline figure (--full): kernel-isolated and steady-state periods, the exchange alone, the
+    # fused Euler step, the advance pattern; the cell-order study, the roofline and the CPU baselines follow below
+    if args.full:
+        # ---- dominant kernel: average duration with HIP events on the launch stream (one rhs call = ONE launch)
+        k_iters = max(10, min(args.steps, 50))
+        starts = [torch.cuda.Event(enable_timing=True) for _ in range(k_iters)]
+        ends = [torch.cuda.Event(enable_timing=True) for _ in range(k_iters)]
+
+        def kernel_only():
+            if self_halo is not None:
+                return step()
+            if args.second_order and halo is not None:
+                # the ghost gradients of the last timed step are still in place: the flux launch alone
+                op.apply_phase(0, True, case.dt, u, f, reset_diagnostics=True, gradients_ready=True)
+            else:
+                op.rhs_function(case.dt, u, f)
+
+        for i in range(k_iters):
+            starts[i].record()
             kernel_only()
-        evs = [torch.cuda.Event(enable_timing=True) for _ in range(13)]
-        evs[0].record()
-        for b in range(12):
-            for _ in range(10):
+            ends[i].record()
+        torch.cuda.synchronize()
+        kern_all = [s.elapsed_time(e) for s, e in zip(starts, ends)]
+        kern_isolated_ms = float(np.mean(kern_all))
+        # the figure the roofline uses: HIP events around the whole timed region / steps (one RHS = one launch, so this is the
+        # launch-to-launch period including the dispatch gap); with several ranks the region also holds the exchange, so the
+        # individually bracketed launches are used there
+        kern_ms = ev0.elapsed_time(ev1) / args.steps if world == 1 else kern_isolated_ms
+
+        # steady state: the launch-to-launch period of back-to-back launches, median over batches (what a long run sees)
+        periods = []
+        if world == 1:
+            for _ in range(40):
                 kernel_only()
-            evs[b + 1].record()
-        torch.cuda.synchronize()
-        periods = [evs[b].elapsed_time(evs[b + 1]) / 10 for b in range(12)]
-    period_median_ms = float(np.median(periods)) if periods else None
+            evs = [torch.cuda.Event(enable_timing=True) for _ in range(13)]
+            evs[0].record()
+            for b in range(12):
+                for _ in range(10):
+                    kernel_only()
+                evs[b + 1].record()
+            torch.cuda.synchronize()
+            periods = [evs[b].elapsed_time(evs[b + 1]) / 10 for b in range(12)]
+        period_median_ms = float(np.median(periods)) if periods else None
 
-    # multi-GPU: the ghost update on its own (pack, P2P over RCCL, unpack), not overlapped
-    halo_ms = timed(lambda: halo.exchange(u), k_iters, lead=5) if halo is not None else None
+        # multi-GPU: the ghost update on its own (pack, P2P over RCCL, unpack), not overlapped
+        halo_ms = timed(lambda: halo.exchange(u), k_iters, lead=5) if halo is not None else None
 
-    # ---- extra (not the metric): one whole forward-Euler step, the update fused into the RHS kernel's stores
-    # (rdyhip_euler_step, F never written) against the RHS + axpy pair -- SURVEY.md 8.f row 1
-    u2 = torch.empty_like(u)
-    u3 = u.clone()
+        # ---- extra (not the metric): one whole forward-Euler step, the update fused into the RHS kernel's stores
+        # (rdyhip_euler_step, F never written) against the RHS + axpy pair -- SURVEY.md 8.f row 1
+        u2 = torch.empty_like(u)
+        u3 = u.clone()
 
-    # with a halo the two state arrays ping-pong as a time loop's do (dt = 0: the same work, the state stays put), so that the
-    # pack of each exchange can ride on the previous step's kernel (rdyhip_halo_fuse_pack) -- the chain a run of steps has
-    pack_fused = False
-    if halo is not None and halo._halo is not None:
-        pack_fused = halo.fuse_pack(True)
-    elif self_halo is not None:
-        pack_fused = self_halo[0].rdyhip_halo_fuse_pack(self_halo[1], 1) == 0
-    pp = [u, u2]
-    if halo is not None or self_halo is not None:
-        u2.copy_(u)
-
-    def fused_step():
-        if halo is not None:
-            halo.step_overlapped(op, 0.0, pp[0], pp[1])
-            pp.reverse()
+        # with a halo the two state arrays ping-pong as a time loop's do (dt = 0: the same work, the state stays put), so that the
+        # pack of each exchange can ride on the previous step's kernel (rdyhip_halo_fuse_pack) -- the chain a run of steps has
+        pack_fused = False
+        if halo is not None and halo._halo is not None:
+            pack_fused = halo.fuse_pack(True)
         elif self_halo is not None:
-            _lib.check(self_halo[0].rdyhip_euler_step_overlapped(op._h, self_halo[1], 0.0, int(pp[0].data_ptr()), int(pp[1].data_ptr()), None,
-                                                                 int(torch.cuda.current_stream().cuda_stream)))
-            pp.reverse()
-        else:
-            op.euler_step(case.dt, u, u2)
+            pack_fused = self_halo[0].rdyhip_halo_fuse_pack(self_halo[1], 1) == 0
+        pp = [u, u2]
+        if halo is not None or self_halo is not None:
+            u2.copy_(u)
 
-    def pair_step():
-        step()
-        op.axpy_owned(0.0, f, u3)      # dt = 0: same traffic, the scratch state stays put
+        def fused_step():
+            if halo is not None:
+                halo.step_overlapped(op, 0.0, pp[0], pp[1])
+                pp.reverse()
+            elif self_halo is not None:
+                _lib.check(self_halo[0].rdyhip_euler_step_overlapped(op._h, self_halo[1], 0.0, int(pp[0].data_ptr()), int(pp[1].data_ptr()), None,
+                                                                     int(torch.cuda.current_stream().cuda_stream)))
+                pp.reverse()
+            else:
+                op.euler_step(case.dt, u, u2)
 
-    ef, ep = timed(fused_step, 60), timed(pair_step, 60)
-    euler = {"fused_ms_per_step": round(ef, 5), "rhs_plus_axpy_ms_per_step": round(ep, 5), "fused_steps_per_s": round(1e3 / ef, 1)}
-    if halo is not None or self_halo is not None:
-        euler["pack_fused_into_kernel"] = bool(pack_fused)
-        if halo is not None:
-            halo.invalidate()
-    # ---- extra (not the metric): the drop-in's real loop, not back-to-back launches.  RDyAdvance (src/rdyadvance.c:261-383) as
-    # the driver's time loop calls it: refresh of the rain source from a host array (RDySetDomainWaterSource -> the
-    # stream-ordered setter), 20 explicit steps, the Courant struct read back (a synchronisation, as with adaptive dt) -- the
-    # device restarts from idle every interval and runs its next few dozen launches 20-35 % slow
-    advance = None
-    if world == 1 and halo is None and self_halo is None:
-        rain = np.full(n_owned, 1e-5)
-        src_before = op.external_sources.clone()
+        def pair_step():
+            step()
+            op.axpy_owned(0.0, f, u3)      # dt = 0: same traffic, the scratch state stays put
 
-        def one_advance(nsteps=20, sync=True):
-            op.set_domain_external_source(0, rain, ordered=True)
-            cur, nxt = u, u2
-            for _ in range(nsteps):
-                op.euler_step(0.0, cur, nxt)       # dt = 0: every interval does the same work
-                cur, nxt = nxt, cur
-            if sync:
-                op.update_diagnostics()
+        ef, ep = timed(fused_step, 60), timed(pair_step, 60)
+        euler = {"fused_ms_per_step": round(ef, 5), "rhs_plus_axpy_ms_per_step": round(ep, 5), "fused_steps_per_s": round(1e3 / ef, 1)}
+        if halo is not None or self_halo is not None:
+            euler["pack_fused_into_kernel"] = bool(pack_fused)
+            if halo is not None:
+                halo.invalidate()
+        # ---- extra (not the metric): the drop-in's real loop, not back-to-back launches.  RDyAdvance (src/rdyadvance.c:261-383) as
+        # the driver's time loop calls it: refresh of the rain source from a host array (RDySetDomainWaterSource -> the
+        # stream-ordered setter), 20 explicit steps, the Courant struct read back (a synchronisation, as with adaptive dt) -- the
+        # device restarts from idle every interval and runs its next few dozen launches 20-35 % slow
+        advance = None
+        if world == 1 and halo is None and self_halo is None:
+            rain = np.full(n_owned, 1e-5)
+            src_before = op.external_sources.clone()
 
-        u2.copy_(u)
-        rows = {}
-        for name, sync in (("adaptive_dt", True), ("fixed_dt", False)):
-            one_advance(sync=sync)
-            torch.cuda.synchronize()
-            t_a = time.perf_counter()
-            for _ in range(12):
+            def one_advance(nsteps=20, sync=True):
+                op.set_domain_external_source(0, rain, ordered=True)
+                cur, nxt = u, u2
+                for _ in range(nsteps):
+                    op.euler_step(0.0, cur, nxt)       # dt = 0: every interval does the same work
+                    cur, nxt = nxt, cur
+                if sync:
+                    op.update_diagnostics()
+
+            u2.copy_(u)
+            rows = {}
+            for name, sync in (("adaptive_dt", True), ("fixed_dt", False)):
                 one_advance(sync=sync)
+                torch.cuda.synchronize()
+                t_a = time.perf_counter()
+                for _ in range(12):
+                    one_advance(sync=sync)
+                torch.cuda.synchronize()
+                rows[name] = (time.perf_counter() - t_a) / (12 * 20) * 1e3
+            op.refresh_field(1, src_before)
             torch.cuda.synchronize()
-            rows[name] = (time.perf_counter() - t_a) / (12 * 20) * 1e3
-        op.refresh_field(1, src_before)
-        torch.cuda.synchronize()
-        advance = {"steps_per_advance": 20, "advances": 12,
-                   "refresh": "domain-wide rain source from a host array (8 B per cell) through the stream-ordered setter, every advance",
-                   "ms_per_step_adaptive_dt": round(rows["adaptive_dt"], 5), "ms_per_step_fixed_dt": round(rows["fixed_dt"], 5),
-                   "back_to_back_ms_per_step": round(ef, 5),
-                   "vs_back_to_back_adaptive_dt": round(rows["adaptive_dt"] / ef, 4), "vs_back_to_back_fixed_dt": round(rows["fixed_dt"] / ef, 4),
-                   "note": "adaptive_dt: the 16-byte Courant struct is read back after every advance (src/rdyadvance.c:366-372), so the device "
-                           "idles between advances; fixed_dt: nothing synchronises"}
-        del src_before
-    del u2, u3, pp
-    step()   # leave F and the diagnostics of a plain RHS evaluation behind for the sanity checks below
+            advance = {"steps_per_advance": 20, "advances": 12,
+                       "refresh": "domain-wide rain source from a host array (8 B per cell) through the stream-ordered setter, every advance",
+                       "ms_per_step_adaptive_dt": round(rows["adaptive_dt"], 5), "ms_per_step_fixed_dt": round(rows["fixed_dt"], 5),
+                       "back_to_back_ms_per_step": round(ef, 5),
+                       "vs_back_to_back_adaptive_dt": round(rows["adaptive_dt"] / ef, 4), "vs_back_to_back_fixed_dt": round(rows["fixed_dt"] / ef, 4),
+                       "note": "adaptive_dt: the 16-byte Courant struct is read back after every advance (src/rdyadvance.c:366-372), so the device "
+                               "idles between advances; fixed_dt: nothing synchronises"}
+            del src_before
+        del u2, u3, pp
+        step()   # leave F and the diagnostics of a plain RHS evaluation behind for the sanity checks below
 
     # sanity: the result is finite and the Courant diagnostic is alive (cross-rank struct-max, src/operator.c:705-751)
     from rdycore_amd.timestep import reduce_courant
@@ -771,7 +816,7 @@ def run_rank(args, argv):
         per_rank = [mine_info]
 
     order_study = None
-    if rank == 0 and world == 1 and args.workload == "c3" and not args.no_order_study and args.emulate_world <= 1 \
+    if args.full and rank == 0 and world == 1 and args.workload == "c3" and not args.no_order_study and args.emulate_world <= 1 \
             and not args.second_order and not args.hr:
         # SURVEY.md 8.d "report both": the same mesh in the generator's row-major numbering and along a Hilbert curve
         order_study = {args.order: round(n_owned / period_median_ms / 1e3, 1)}
@@ -793,10 +838,6 @@ def run_rank(args, argv):
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         value = total_cells / (elapsed / args.steps) / 1e6
-        info = op.layout_info()
-        quads = info["slots_per_cell"] == 4
-        alg = ALG_BYTES_PER_CELL_QUADS if quads else ALG_BYTES_PER_CELL
-        achieved = n_owned * alg / (kern_ms * 1e-3) / 1e9
         nxg = args.nx if (args.scaling == "strong" or world == 1) else args.nx * world
         part = "single" if world == 1 else (f"rcb_{world}" if args.scaling == "strong" else f"strips_x{world}")
         if world == 1 and args.emulate_world > 1:
@@ -833,14 +874,6 @@ def run_rank(args, argv):
             workload = (f"C5 stand-in for the Harvey mesh: synthetic {nxg}x{args.ny}x2 triangles over a rough analytic DEM (ramp + 3 sinusoids), "
                         f"{total_cells} cells in this run ({n_owned} on rank 0), {dry:.0%} of them dry, rain 1e-5 m/s, Manning 0.03, "
                         f"critical-outflow segment + reflecting walls, hydrostatic reconstruction, {friction}, dt = 0.05 s")
-        traffic, traffic_src = (None, None)
-        if world == 1:
-            traffic, traffic_src = load_traffic(traffic_key(args), int(info["bytes_per_apply"]), args.second_order)
-        if args.second_order:
-            kname = "swe_rhs_muscl_fused_kernel<%d,%d>" % (info["slots_per_cell"], 0 if args.source == "semi_implicit" else 1)
-        else:
-            kname = "%s<%d,%d%s>" % ("swe_rhs_tiled_kernel" if info["tiled_kernel"] else "swe_rhs_kernel", info["slots_per_cell"],
-                                     0 if args.source == "semi_implicit" else 1, ",HR" if args.hr else "")
         out = {
             "metric": "M cell-updates/s (SWE RHS eval)",
             "value": round(value, 1),
@@ -877,60 +910,73 @@ def run_rank(args, argv):
                                         if n_cond else "none"),
                        "setup_seconds": round(setup_s, 1), "setup_stages": stages, "per_rank": per_rank, "max_courant": cd.max_courant_num,
                        "max_courant_edge": cd.global_edge_id, "max_courant_cell": cd.global_cell_id, "finite": finite},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBPS, 4),
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "kernel": kname,
-                         "algorithmic_bytes_per_cell": alg,
-                         "tile_edge_records_per_cell": round(info["num_edge_records"] / max(n_owned, 1), 4),
-                         "halo_cells_per_tile": round(info["num_halo_entries"] / max(info["num_tiles"], 1), 2),
-                         "kernel_avg_ms": round(kern_ms, 5),
-                         "kernel_isolated_avg_ms": round(kern_isolated_ms, 5), "kernel_isolated_median_ms": round(float(np.median(kern_all)), 5),
-                         "kernel_isolated_min_ms": round(float(np.min(kern_all)), 5),
-                         "steady_state_period_median_ms": round(period_median_ms, 5) if period_median_ms else None,
-                         "steady_state_frac": round(n_owned * alg / (period_median_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4) if period_median_ms else None,
-                         "algorithmic_bytes_per_launch": int(n_owned * alg),
-                         "layout_bytes_per_launch": int(info["bytes_per_apply"]),
-                         "persistent_workgroups": int(info["persistent_grid"]), "lds_bytes_per_workgroup": int(info["lds_bytes"]),
-                         "cells_per_tile": round(n_owned / max(info["num_tiles"], 1), 1)},
         }
-        if quads:
-            out["roofline"]["frac_176B_model"] = round(n_owned * ALG_BYTES_PER_CELL / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)
-        # the whole forward-Euler step by the same byte model (it stores u_out where the RHS stores F; F itself is not written)
-        euler["frac_of_hbm_roofline"] = round(n_owned * alg / (euler["fused_ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)
-        if world == 1 and halo is None and self_halo is None:
-            # PMC bytes of the Euler-step kernel itself, from the same profiled runs (their Euler launches), same guard
-            et, esrc = load_traffic(traffic_key(args) + "_euler_step", int(info["bytes_per_apply"]), args.second_order, quiet=True)
-            euler["traffic"], euler["traffic_source"] = et, esrc
-        out["euler_step"] = euler
-        if advance is not None:
-            out["advance_pattern"] = advance
-        if order_study:
-            out["cell_order_study"] = order_study
-        if args.second_order:
-            # the 176-B figure above keeps variants comparable; the second-order path's own model:
-            b2 = ALG_BYTES_PER_CELL_SECOND_ORDER
-            if quads:      # two edges per cell instead of 1.5: 192 + centroid 16 + midpoints 2 x 16
-                b2 += ALG_BYTES_PER_CELL_QUADS - ALG_BYTES_PER_CELL + 8.0
-            a2 = n_owned * b2 / (kern_ms * 1e-3) / 1e9
-            out["roofline"]["second_order_model"] = {"bytes_per_cell_update": b2, "achieved": round(a2, 1),
-                                                     "frac": round(a2 / HBM_PEAK_GBPS, 4)}
-        if not args.no_cpu_baseline and world == 1:
-            # the reference's CPU path beside the GPU figure, ON THE BENCHMARK MESH ITSELF where it fits (C3's
-            # 10 M cells, ~1 s per RHS on one core); the 1 M-cell sample of earlier rounds stays as a second key
-            full = case if (n_owned <= CPU_FULL_MESH_MAX_CELLS and args.emulate_world <= 1) else None
-            out["cpu_baseline"] = cpu_baseline(args, full)
-            if full is not None:
-                out["cpu_baseline_sample"] = cpu_baseline(args)
-            if not args.no_cpu_all_cores:
-                try:
-                    out["cpu_baseline_openmp"] = cpu_baseline_openmp(args, full)     # all host cores, one process, the benchmark mesh
-                except Exception as exc:  # a reported extra, never a reason to lose the bench line
-                    out["cpu_baseline_openmp"] = {"error": repr(exc)}
-                try:
-                    out["cpu_baseline_all_cores"] = cpu_baseline_all_cores(args, argv)   # one process per core on the parts of the sample
-                except Exception as exc:
-                    out["cpu_baseline_all_cores"] = {"error": repr(exc)}
+        if args.full:
+            info = op.layout_info()
+            quads = info["slots_per_cell"] == 4
+            alg = ALG_BYTES_PER_CELL_QUADS if quads else ALG_BYTES_PER_CELL
+            achieved = n_owned * alg / (kern_ms * 1e-3) / 1e9
+            traffic, traffic_src = (None, None)
+            if world == 1:
+                traffic, traffic_src = load_traffic(traffic_key(args), int(info["bytes_per_apply"]), args.second_order)
+            if args.second_order:
+                kname = "swe_rhs_muscl_fused_kernel<%d,%d>" % (info["slots_per_cell"], 0 if args.source == "semi_implicit" else 1)
+            else:
+                kname = "%s<%d,%d%s>" % ("swe_rhs_tiled_kernel" if info["tiled_kernel"] else "swe_rhs_kernel", info["slots_per_cell"],
+                                         0 if args.source == "semi_implicit" else 1, ",HR" if args.hr else "")
+            out["roofline"] = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                               "frac": round(achieved / HBM_PEAK_GBPS, 4),
+                               "traffic": traffic, "traffic_source": traffic_src,
+                               "kernel": kname,
+                               "algorithmic_bytes_per_cell": alg,
+                               "tile_edge_records_per_cell": round(info["num_edge_records"] / max(n_owned, 1), 4),
+                               "halo_cells_per_tile": round(info["num_halo_entries"] / max(info["num_tiles"], 1), 2),
+                               "kernel_avg_ms": round(kern_ms, 5),
+                               "kernel_isolated_avg_ms": round(kern_isolated_ms, 5), "kernel_isolated_median_ms": round(float(np.median(kern_all)), 5),
+                               "kernel_isolated_min_ms": round(float(np.min(kern_all)), 5),
+                               "steady_state_period_median_ms": round(period_median_ms, 5) if period_median_ms else None,
+                               "steady_state_frac": round(n_owned * alg / (period_median_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4) if period_median_ms else None,
+                               "algorithmic_bytes_per_launch": int(n_owned * alg),
+                               "layout_bytes_per_launch": int(info["bytes_per_apply"]),
+                               "persistent_workgroups": int(info["persistent_grid"]), "lds_bytes_per_workgroup": int(info["lds_bytes"]),
+                               "cells_per_tile": round(n_owned / max(info["num_tiles"], 1), 1)}
+            if quads:
+                out["roofline"]["frac_176B_model"] = round(n_owned * ALG_BYTES_PER_CELL / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)
+            # the whole forward-Euler step by the same byte model (it stores u_out where the RHS stores F; F itself is not written)
+            euler["frac_of_hbm_roofline"] = round(n_owned * alg / (euler["fused_ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)
+            if world == 1 and halo is None and self_halo is None:
+                # PMC bytes of the Euler-step kernel itself, from the same profiled runs (their Euler launches), same guard
+                et, esrc = load_traffic(traffic_key(args) + "_euler_step", int(info["bytes_per_apply"]), args.second_order, quiet=True)
+                euler["traffic"], euler["traffic_source"] = et, esrc
+            out["euler_step"] = euler
+            if advance is not None:
+                out["advance_pattern"] = advance
+            if order_study:
+                out["cell_order_study"] = order_study
+            if args.second_order:
+                # the 176-B figure above keeps variants comparable; the second-order path's own model:
+                b2 = ALG_BYTES_PER_CELL_SECOND_ORDER
+                if quads:      # two edges per cell instead of 1.5: 192 + centroid 16 + midpoints 2 x 16
+                    b2 += ALG_BYTES_PER_CELL_QUADS - ALG_BYTES_PER_CELL + 8.0
+                a2 = n_owned * b2 / (kern_ms * 1e-3) / 1e9
+                out["roofline"]["second_order_model"] = {"bytes_per_cell_update": b2, "achieved": round(a2, 1),
+                                                         "frac": round(a2 / HBM_PEAK_GBPS, 4)}
+            if not args.no_cpu_baseline and world == 1:
+                # the reference's CPU path beside the GPU figure, ON THE BENCHMARK MESH ITSELF where it fits (C3's
+                # 10 M cells, ~1 s per RHS on one core); the 1 M-cell sample of earlier rounds stays as a second key
+                full = case if (n_owned <= CPU_FULL_MESH_MAX_CELLS and args.emulate_world <= 1) else None
+                out["cpu_baseline"] = cpu_baseline(args, full)
+                if full is not None:
+                    out["cpu_baseline_sample"] = cpu_baseline(args)
+                if not args.no_cpu_all_cores:
+                    try:
+                        out["cpu_baseline_openmp"] = cpu_baseline_openmp(args, full)     # all host cores, one process, the benchmark mesh
+                    except Exception as exc:  # a reported extra, never a reason to lose the bench line
+                        out["cpu_baseline_openmp"] = {"error": repr(exc)}
+                    try:
+                        out["cpu_baseline_all_cores"] = cpu_baseline_all_cores(args, argv)   # one process per core on the parts of the sample
+                    except Exception as exc:
+                        out["cpu_baseline_all_cores"] = {"error": repr(exc)}
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
     if halo is not None:

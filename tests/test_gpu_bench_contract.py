@@ -1,9 +1,11 @@
-"""GPU: bench.py prints ONE JSON line with the keys the driver's contract names (small mesh, a few steps)."""
+"""GPU: bench.py prints ONE JSON line with the keys the driver's contract names (small mesh, a few steps): the headline
+figure alone in a plain run, every extra with --full; --dump-outputs writes what the last timed step computed."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,7 +21,7 @@ def test_bench_line_has_the_contract_keys(extra, rdyhip_kernel):
     if rdyhip_kernel == "cell":
         pytest.skip("one kernel variant is enough")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--nx", "120", "--ny", "90",
-           "--cpu-sample", "60x40", "--no-cpu-all-cores", "--condition-seconds", "0.1"] + extra
+           "--cpu-sample", "60x40", "--no-cpu-all-cores", "--condition-seconds", "0.1", "--full"] + extra
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -67,3 +69,35 @@ def test_bench_line_has_the_contract_keys(extra, rdyhip_kernel):
         f1 = d["config"]["per_rank"][0]["rhs_step_form"]
         assert f1["form"] in ("in_order", "two_streams") and f1["source"] in ("measured", "trial_running", "forced")
     assert d["value"] > 0 and abs(d["value"] - d["config"]["cells_per_gpu"] / d["ms_per_step"] / 1e3) <= 1e-3 * d["value"] + 0.11
+
+
+def test_plain_bench_line_and_dumped_outputs(rdyhip_kernel, tmp_path):
+    """a plain run: --steps timed steps, the headline keys and config, none of the --full extras; --dump-outputs: F of the
+    last timed step equals the oracle's RHS of the same case, and the Courant number its launch left equals the oracle's"""
+    sys.path.insert(0, ROOT)
+    import bench
+    from helpers import oracle_from_case, rel_linf
+    # second order is implemented by the tiled kernels only
+    for extra in ([], ["--second-order"]) if rdyhip_kernel == "tiled" else ([],):
+        argv = ["--gpus", "1", "--steps", "7", "--warmup", "2", "--nx", "120", "--ny", "90", "--condition-seconds", "0.1"] + extra
+        dump = tmp_path / ("so" if extra else "fo")
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv + ["--dump-outputs", str(dump)],
+                             capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, lines
+        d = json.loads(lines[0])
+        assert d["metric"] == "M cell-updates/s (SWE RHS eval)" and d["unit"] == "M cell-updates/s" and d["higher_is_better"] is True
+        assert d["dtype"] == "f64" and d["steps"] == 7 and d["warmup"] == 2 and d["ms_per_step"] > 0 and d["config"]["finite"] is True
+        assert abs(d["value"] - d["config"]["cells_per_gpu"] / d["ms_per_step"] / 1e3) <= 1e-3 * d["value"] + 0.11
+        assert not {"roofline", "euler_step", "advance_pattern", "cell_order_study", "cpu_baseline"} & set(d)
+        case = bench.build_case(bench.parse(argv), 0, 1)
+        orc = oracle_from_case(case)
+        ref = orc.apply(case.dt, case.u_local)
+        rhs, rows, courant = (np.load(dump / (n + ".npy")) for n in ("rhs", "rhs_rows", "courant"))
+        assert rhs.dtype == np.float64 and rhs.shape == (case.mesh.num_owned_cells, 3)
+        assert np.array_equal(rows, np.arange(case.mesh.num_owned_cells))
+        assert rel_linf(rhs, ref) <= 1e-10, extra
+        assert courant.shape == (3,) and courant[0] == d["config"]["max_courant"]
+        # to rounding: FMA contraction (first order), gradients formed on the chip (second order; tests/test_gpu_parity.py)
+        assert abs(courant[0] - orc.diagnostics()[0]) <= (1e-10 if extra else 1e-12) * max(1.0, courant[0]), extra

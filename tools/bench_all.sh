@@ -22,6 +22,7 @@ V[houston_l7_hr]="--workload houston_refined --levels 7 --hr --no-cpu-all-cores"
 V[delaunay]="--workload delaunay --no-cpu-all-cores"
 V[self_exchange]="--emulate-world 3 --emulate-rank 1 --self-exchange --no-cpu-baseline"
 V[self_exchange_so]="--emulate-world 3 --emulate-rank 1 --self-exchange --second-order --no-cpu-baseline"
+for tag in "${!V[@]}"; do V[$tag]="--full ${V[$tag]}"; done   # every line with its extras (roofline, euler_step, CPU baselines)
 ORDER="${@:-c3 c3_200 hr xq c2 quads c5 so so_quads houston houston_hr houston_natural houston_so delaunay self_exchange self_exchange_so}"
 mkdir -p gpurun_out
 for tag in $ORDER; do

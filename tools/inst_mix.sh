@@ -2,7 +2,7 @@
 # Dynamic instruction mix of the RHS kernel from rocprofv3 PMC passes (GPU box).  usage: tools/inst_mix.sh <tag> [bench args]
 TAG=${1:-mix}; shift || true
 REPO=$(pwd); OUT=$REPO/gpurun_out/mix_$TAG; mkdir -p $OUT; export TMPDIR=/tmp
-BARGS="--steps 20 --warmup 5 --no-cpu-baseline --no-order-study --condition-seconds 0.1 $@"
+BARGS="--full --steps 20 --warmup 5 --no-cpu-baseline --no-order-study --condition-seconds 0.1 $@"
 cd /tmp
 i=0
 for set in "SQ_INSTS_VALU SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_TRANS_F64" \

@@ -3,7 +3,7 @@
 # passes on the GPU box: where a kernel that saturates neither HBM bytes nor VALU waits.  usage: tools/mem_pipe.sh <tag> [bench args]
 TAG=${1:-mem}; shift || true
 REPO=$(pwd); OUT=$REPO/gpurun_out/mem_$TAG; mkdir -p $OUT; export TMPDIR=/tmp
-BARGS="--steps 20 --warmup 5 --no-cpu-baseline --no-order-study --condition-seconds 0.1 $@"
+BARGS="--full --steps 20 --warmup 5 --no-cpu-baseline --no-order-study --condition-seconds 0.1 $@"
 cd /tmp
 i=0
 for set in "TA_TA_BUSY_sum TA_FLAT_READ_WAVEFRONTS_sum GRBM_GUI_ACTIVE" \

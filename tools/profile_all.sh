@@ -32,7 +32,7 @@ timeout -k 10 200 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv 
 timeout -k 10 200 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $CAL/cal_write -o pmc -- python3 $REPO/tools/calib_traffic.py > $CAL/calib_write.log 2>&1 || echo "calibration (write) failed"
 for tag in $ORDER; do
   OUT=$REPO/gpurun_out/prof_${ROUND}_$tag; mkdir -p $OUT
-  BARGS="--steps 20 --warmup 5 --no-cpu-baseline --no-order-study ${V[$tag]}"
+  BARGS="--full --steps 20 --warmup 5 --no-cpu-baseline --no-order-study ${V[$tag]}"   # --full: the Euler-step launches are profiled too
   PARGS="$BARGS --condition-seconds 0.2"
   echo "variant $tag: $BARGS"
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python3 $REPO/bench.py $BARGS > $OUT/bench_trace.log 2>&1 || echo "  trace failed"

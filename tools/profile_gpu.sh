@@ -7,7 +7,7 @@ REPO=$(pwd)
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-BARGS="--steps 20 --warmup 5 --no-cpu-baseline --no-order-study $@"
+BARGS="--full --steps 20 --warmup 5 --no-cpu-baseline --no-order-study $@"   # --full: the Euler-step launches are profiled too
 PARGS="$BARGS --condition-seconds 0.2"   # counter passes: fewer launches
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python3 $REPO/bench.py $BARGS > $OUT/bench_trace.log 2>&1

@@ -10,7 +10,7 @@ for sz in $SIZES; do
   nx=${sz%x*}; ny=${sz#*x}
   for lib in ab_libs/*.so; do
     for tc in $TILES; do
-      RDYHIP_TILE_CELLS=$tc RDYHIP_LIB=$PWD/$lib python3 bench.py --no-cpu-baseline --no-order-study --steps 200 --warmup 20 --condition-seconds 0.3 --nx $nx --ny $ny "$@" 2>/dev/null | \
+      RDYHIP_TILE_CELLS=$tc RDYHIP_LIB=$PWD/$lib python3 bench.py --full --no-cpu-baseline --no-order-study --steps 200 --warmup 20 --condition-seconds 0.3 --nx $nx --ny $ny "$@" 2>/dev/null | \
         python3 -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; n=d['config']['cells_per_gpu']; p=r['steady_state_period_median_ms']; print(n, '$(basename $lib .so)', $tc, round(1e3*p,2), round(1e3*d['euler_step']['fused_ms_per_step'],2), round(n/p/1e3,1), round(n*176/p/1e6,1), r['persistent_workgroups'], r.get('cells_per_tile'))"
     done
   done

@@ -3,7 +3,7 @@
 # One rank's part of an 8-way RCB partition on ONE GPU, the real multi-rank step (rdyhip_rhs_overlapped) with its exchange
 # looped back through a one-rank RCCL communicator (--self-exchange), beside the plain single-launch RHS of the same part.
 # usage: tools/small_partitions.sh > gpurun_out/small_partitions.txt
-B="--steps 200 --warmup 20 --no-cpu-baseline --no-order-study"
+B="--full --steps 200 --warmup 20 --no-cpu-baseline --no-order-study"
 pick='import sys,json; d=json.loads(sys.stdin.read()); r=d["roofline"]; c=d["config"]; print(sys.argv[1], "cells", c["cells_per_gpu"], "ms/step", d["ms_per_step"], "frac", r["frac"], "kernel_ms", r["kernel_avg_ms"], "halo_B", c.get("halo_bytes_per_rank"), "tiles/grid", r.get("persistent_workgroups"), "euler_fused_ms", d["euler_step"]["fused_ms_per_step"])'
 run() { tag=$1; shift; python3 bench.py $B "$@" 2>/dev/null | python3 -c "$pick" "$tag"; }
 # the reference's 2.88 M-quad dam break (docs/user/example-cases/dam-break/index.md:24-26) and a 2.8 M-cell refined Houston mesh, 8 ranks
