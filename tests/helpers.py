@@ -4,10 +4,11 @@ import numpy as np
 from oracle import oracle as O
 
 
-def oracle_from_case(case):
+def oracle_from_case(case, **kw):
+    """kw: further OracleOperator options (all_edges_local)"""
     cfg = case.config
     orc = O.OracleOperator(case.mesh, case.condition_types, cfg.tiny_h, cfg.h_anuga_regular, cfg.xq2018_threshold, cfg.source_method, cfg.well_balancing,
-                           second_order=cfg.second_order, limiter=cfg.limiter)
+                           second_order=cfg.second_order, limiter=cfg.limiter, **kw)
     orc.mannings[:] = case.mannings
     orc.external_sources[:] = case.ext_src
     for b, vals in case.boundary_values.items():

@@ -14,58 +14,11 @@ from rdycore_amd import mesh as M
 from rdycore_amd.operator import RDyFlowConfig
 
 from helpers import oracle_from_case, rel_linf
+from random_cases import random_case, random_tri_mesh
 from test_gpu_parity import check_all, run_both
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-10
-
-
-def random_tri_mesh(rng, nx, ny, project_2d=False):
-    ii, jj = np.meshgrid(np.arange(nx + 1), np.arange(ny + 1), indexing="xy")
-    x = ii.ravel().astype(float)
-    y = jj.ravel().astype(float)
-    inner = (ii.ravel() > 0) & (ii.ravel() < nx) & (jj.ravel() > 0) & (jj.ravel() < ny)
-    x[inner] += rng.uniform(-0.3, 0.3, inner.sum())
-    y[inner] += rng.uniform(-0.3, 0.3, inner.sum())
-    z = 0.3 * np.sin(0.7 * x) * np.cos(0.5 * y) + 0.05 * rng.normal(size=x.size)
-    xyz = np.stack([x, y, z], axis=1)
-    v = lambda i, j: j * (nx + 1) + i
-    conn = []
-    for j in range(ny):
-        for i in range(nx):
-            if rng.random() < 0.5:
-                conn += [[v(i, j), v(i + 1, j), v(i + 1, j + 1)], [v(i, j), v(i + 1, j + 1), v(i, j + 1)]]
-            else:
-                conn += [[v(i, j), v(i + 1, j), v(i, j + 1)], [v(i + 1, j), v(i + 1, j + 1), v(i, j + 1)]]
-    conn = np.array(conn, dtype=np.int32)
-    conn = conn[rng.permutation(conn.shape[0])]
-    return M.build_mesh(xyz, conn, boundary_classifier=M.box_side_boundaries(0, nx, 0, ny), project_2d=project_2d)
-
-
-def random_case(rng, mesh, cfg):
-    nc = mesh.num_cells
-    kind = rng.integers(0, 5, nc)
-    if cfg.second_order:
-        # linear extrapolation next to films of 1e-7..1e-2 m gives velocities of 1e6 m/s and |F| ~ 1e11 in the reference
-        # too, which would make the relative L-inf bar meaningless: dry or deep cells only
-        kind = np.where((kind == 1) | (kind == 2), 3, kind)
-    h = np.where(kind == 0, 0.0,                                        # dry
-        np.where(kind == 1, cfg.tiny_h * rng.uniform(0.2, 3.0, nc),     # around the wet/dry threshold
-        np.where(kind == 2, rng.uniform(1e-4, 1e-2, nc),                # thin films
-                 rng.uniform(0.2, 3.0, nc))))                           # deep
-    speed = np.where(rng.random(nc) < 0.3, rng.uniform(3.0, 12.0, nc), rng.uniform(0.0, 1.5, nc))   # some supercritical
-    ang = rng.uniform(0, 2 * np.pi, nc)
-    u = np.stack([h, h * speed * np.cos(ang), h * speed * np.sin(ang)], axis=1)
-    ctypes, bvals = [], {}
-    for i, b in enumerate(mesh.boundaries):
-        t = [M.CONDITION_DIRICHLET, M.CONDITION_REFLECTING, M.CONDITION_CRITICAL_OUTFLOW, M.CONDITION_DIRICHLET][i % 4]
-        ctypes.append(t)
-        if t == M.CONDITION_DIRICHLET:
-            hb = np.where(rng.random(b.num_edges) < 0.2, 0.0, rng.uniform(0.1, 2.0, b.num_edges))
-            bvals[i] = np.stack([hb, hb * rng.normal(size=b.num_edges), hb * rng.normal(size=b.num_edges)], axis=1)
-    no = mesh.num_owned_cells
-    src = rng.normal(size=(no, 3)) * np.array([1e-4, 1e-3, 1e-3])
-    return CS.Case("fuzz", mesh, cfg, ctypes, u, rng.uniform(0.01, 0.06, no), src, bvals, float(rng.choice([1e-3, 1e-2, 0.1])))
 
 
 @pytest.mark.parametrize("seed", range(int(os.environ.get("RDYHIP_FUZZ_SEEDS", "6"))))   # RDYHIP_FUZZ_SEEDS=200: a longer soak
