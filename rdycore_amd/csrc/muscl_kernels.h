@@ -21,9 +21,7 @@
 //    data per edge side and evaluates the Roe flux once per edge; phase 2 is the
 //    first-order kernel's (segmented per-cell sum in the reference's order, source
 //    terms, stores).  Boundary edges stay first order (ApplyBoundaryFlux is
-//    unchanged by numerics.second_order).  (A split form -- gradients through
-//    memory, a flux kernel that reads them -- was the A/B partner of rounds 1-4:
-//    tools/probes/split_muscl_form.patch.)
+//    unchanged by numerics.second_order).
 //
 // Across ranks the reference solves each cut edge on the rank that owns it and
 // adds the ghost side back with DMLocalToGlobal(ADD_VALUES).  Here every rank
@@ -40,18 +38,15 @@
 
 namespace rdyhip {
 
-// non-temporal hints for the fused kernel's streamed-once data (see swe_kernels.h)
-#define RDY_MLD(ptr) __builtin_nontemporal_load(ptr)
-#define RDY_MST(ptr, val) __builtin_nontemporal_store((val), (ptr))
-
+// the fused kernel's streamed-once data takes the non-temporal hints of swe_kernels.h (RDY_LD / RDY_ST)
 typedef double   rdy_d2v __attribute__((ext_vector_type(2)));
 typedef uint32_t rdy_u2v __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ double2 load_d2(const double *p) {  // 16-byte aligned pair
-  const rdy_d2v v = RDY_MLD(reinterpret_cast<const rdy_d2v *>(p));
+  const rdy_d2v v = RDY_LD(reinterpret_cast<const rdy_d2v *>(p));
   return make_double2(v.x, v.y);
 }
 __device__ __forceinline__ uint2 load_u2(const void *p) {
-  const rdy_u2v v = RDY_MLD(reinterpret_cast<const rdy_u2v *>(p));
+  const rdy_u2v v = RDY_LD(reinterpret_cast<const rdy_u2v *>(p));
   return make_uint2(v.x, v.y);
 }
 
@@ -224,18 +219,6 @@ __device__ __forceinline__ EdgeFlux muscl_edge(const KernelArgs &a, int tile, do
   return r;
 }
 
-// index of slot s's edge in the tile's edge list, or -1 for an unused slot
-template <int S>
-__device__ __forceinline__ int slot_edge(uint32_t r0, uint32_t r1, int s) {
-  if (S == 3) {
-    const uint32_t ref = (r0 >> (10 * s)) & 0x3FF;
-    return ref == REF3_EMPTY ? -1 : (int)ref;
-  }
-  const uint32_t w   = (s < 2) ? r0 : r1;
-  const uint32_t ref = (s & 1) ? (w >> 16) : (w & 0xFFFFu);
-  return ref == SLOT_EMPTY ? -1 : (int)ref;
-}
-
 // Phase 2 of both second-order kernels: a cell's flux sum in the reference's edge order + the Courant number
 // (src/swe/swe_petsc.c:184-201); kf[s] = -+len/area of slot s.
 template <int S, class LAY>
@@ -282,9 +265,7 @@ __device__ __forceinline__ void muscl_cell_sum(const KernelArgs &a, uint32_t r0,
 // reference multiplies c_LR and c_RL by q_R - q_L; the signs cancel in w d (q_n - q_c)).
 template <int S>
 __global__ __launch_bounds__(BLOCK) void muscl_gradient_kernel(const KernelArgs a, const MusclArgs g, const double *__restrict__ u) {
-  int tile = blockIdx.x;
-  if (a.xcd_chunks > 0) tile = (blockIdx.x & 7) * a.xcd_chunks + (blockIdx.x >> 3);
-  const int i = tile * BLOCK + threadIdx.x;
+  const int i = xcd_block(a.xcd_chunks) * BLOCK + threadIdx.x;
   if (i >= a.n_work) return;
   const int o = a.list ? a.list[i] : i;
   int32_t   id[S];
@@ -540,7 +521,7 @@ __global__ __launch_bounds__(TILE) void swe_rhs_muscl_fused_kernel(const KernelA
     // unconditional loads with clamped indices (a tile has edges; lanes past the end read the last record, unused): a
     // lane-conditional load costs register copies of the loaded value at its merge -- and a wait in the middle of the batch
     if (S == 3) {
-      r0 = RDY_MLD(&reinterpret_cast<const uint32_t *>(a.slot_ref)[active ? o : td.c_off]);
+      r0 = RDY_LD(&reinterpret_cast<const uint32_t *>(a.slot_ref)[active ? o : td.c_off]);
     } else {
       const uint2 w = load_u2(reinterpret_cast<const uint2 *>(a.slot_ref) + (active ? o : td.c_off));
       r0            = w.x;
@@ -551,11 +532,11 @@ __global__ __launch_bounds__(TILE) void swe_rhs_muscl_fused_kernel(const KernelA
     uint2 bw = make_uint2(ones, ones);
     if (tid < nh) bw = load_u2(g.bn_idx + 4 * ((int64_t)td.h_off + tid));
     const int      e0 = td.e_off + min(tid, ne - 1), e1 = td.e_off + min(tid + TILE, ne - 1);
-    const uint32_t lr0 = RDY_MLD(&a.e_lr[e0]);
-    const double   cs0 = RDY_MLD(&a.e_cs[e0]);
+    const uint32_t lr0 = RDY_LD(&a.e_lr[e0]);
+    const double   cs0 = RDY_LD(&a.e_cs[e0]);
     const double2  md0 = load_d2(g.e_mid + 2 * (int64_t)e0);
-    const uint32_t lr1 = RDY_MLD(&a.e_lr[e1]);
-    const double   cs1 = RDY_MLD(&a.e_cs[e1]);
+    const uint32_t lr1 = RDY_LD(&a.e_lr[e1]);
+    const double   cs1 = RDY_LD(&a.e_cs[e1]);
     const double2  md1 = load_d2(g.e_mid + 2 * (int64_t)e1);
     __builtin_amdgcn_s_setprio(0);
     // ---- phase 0: state + centroid of own cells, first ring, second ring; the tile's edge records -> LDS
@@ -634,13 +615,13 @@ __global__ __launch_bounds__(TILE) void swe_rhs_muscl_fused_kernel(const KernelA
       // loaded values at its merge, and with them a wait for the streams right where they are requested
       const int oc = active ? o : td.c_off;
 #pragma unroll
-      for (int s = 0; s < S; ++s) kf[s] = RDY_MLD(&a.coef[s * a.stride + oc]);
-      dzx  = RDY_MLD(&a.dzdx[oc]);
-      dzy  = RDY_MLD(&a.dzdy[oc]);
-      nman = RDY_MLD(&a.mannings[oc]);
-      s0   = RDY_MLD(&a.extsrc[3 * (int64_t)oc + 0]);
-      s1   = RDY_MLD(&a.extsrc[3 * (int64_t)oc + 1]);
-      s2   = RDY_MLD(&a.extsrc[3 * (int64_t)oc + 2]);
+      for (int s = 0; s < S; ++s) kf[s] = RDY_LD(&a.coef[s * a.stride + oc]);
+      dzx  = RDY_LD(&a.dzdx[oc]);
+      dzy  = RDY_LD(&a.dzdy[oc]);
+      nman = RDY_LD(&a.mannings[oc]);
+      s0   = RDY_LD(&a.extsrc[3 * (int64_t)oc + 0]);
+      s1   = RDY_LD(&a.extsrc[3 * (int64_t)oc + 1]);
+      s2   = RDY_LD(&a.extsrc[3 * (int64_t)oc + 2]);
     };
     EdgeFlux x0 = {0.0, 0.0, 0.0, -1.0}, x1 = x0;
     if (tid < ne) x0 = do_edge(lr0, cs0, md0);
@@ -686,9 +667,9 @@ __global__ __launch_bounds__(TILE) void swe_rhs_muscl_fused_kernel(const KernelA
           wave_store_rows3(a.u_out, base, lane, ncell, n0, n1, n2);
         } else if (active) {
           const int64_t c = a.o2l[o];
-          RDY_MST(&a.u_out[3 * c + 0], n0);
-          RDY_MST(&a.u_out[3 * c + 1], n1);
-          RDY_MST(&a.u_out[3 * c + 2], n2);
+          RDY_ST(&a.u_out[3 * c + 0], n0);
+          RDY_ST(&a.u_out[3 * c + 1], n1);
+          RDY_ST(&a.u_out[3 * c + 2], n2);
         }
         if (td.send()) wave_store_send_rows(a, tile, tid, n0, n1, n2);  // the fused pack of the next state exchange (swe_kernels.h)
       }

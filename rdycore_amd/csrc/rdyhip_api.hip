@@ -30,6 +30,7 @@
 #include <string>
 #include <atomic>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "rdyhip.h"
@@ -207,50 +208,40 @@ using TiledKernelFn = void (*)(const KernelArgs, const double, const double *, d
 void halo_forget_packed_state(RDyHipHalo_s *h);   // halo_exchange.h
 void halo_operator_gone(RDyHipHalo_s *h);
 
-// the instantiation of the tiled kernel for (slots per cell, source method, overwrite, HR, F stored with / without the hint)
-template <bool HR, bool FNT>
-TiledKernelFn tiled_kernel_fn_hr(int S, int src, bool ovw) {
-  if (S == 3) {
-    if (src) return ovw ? swe_rhs_tiled_kernel<3, 1, true, HR, false, FNT> : swe_rhs_tiled_kernel<3, 1, false, HR, false, FNT>;
-    return ovw ? swe_rhs_tiled_kernel<3, 0, true, HR, false, FNT> : swe_rhs_tiled_kernel<3, 0, false, HR, false, FNT>;
-  }
-  if (src) return ovw ? swe_rhs_tiled_kernel<4, 1, true, HR, false, FNT> : swe_rhs_tiled_kernel<4, 1, false, HR, false, FNT>;
-  return ovw ? swe_rhs_tiled_kernel<4, 0, true, HR, false, FNT> : swe_rhs_tiled_kernel<4, 0, false, HR, false, FNT>;
+// std::true_type / std::false_type for a run-time flag: how the two selectors below turn a launch's choices into template arguments
+template <class F>
+auto with_flag(bool b, F f) {
+  return b ? f(std::true_type()) : f(std::false_type());
 }
-TiledKernelFn tiled_kernel_fn(int S, int src, bool ovw, bool hr, bool cached_f = false) {
-  if (cached_f) return hr ? tiled_kernel_fn_hr<true, false>(S, src, ovw) : tiled_kernel_fn_hr<false, false>(S, src, ovw);
-  return hr ? tiled_kernel_fn_hr<true, true>(S, src, ovw) : tiled_kernel_fn_hr<false, true>(S, src, ovw);
-}
-// the instantiation with the forward-Euler update fused into the stores (rdyhip_euler_step); FNT = false: plain (cached)
-// stores of u_out, for states that fit the Infinity Cache
-template <bool HR, bool FNT>
-TiledKernelFn tiled_euler_fn_hr(int S, int src) {
-  if (S == 3) return src ? swe_rhs_tiled_kernel<3, 1, true, HR, true, FNT> : swe_rhs_tiled_kernel<3, 0, true, HR, true, FNT>;
-  return src ? swe_rhs_tiled_kernel<4, 1, true, HR, true, FNT> : swe_rhs_tiled_kernel<4, 0, true, HR, true, FNT>;
-}
-TiledKernelFn tiled_euler_fn(int S, int src, bool hr, bool uout_cached = false) {
-  if (uout_cached) return hr ? tiled_euler_fn_hr<true, false>(S, src) : tiled_euler_fn_hr<false, false>(S, src);
-  return hr ? tiled_euler_fn_hr<true, true>(S, src) : tiled_euler_fn_hr<false, true>(S, src);
+
+// The instantiation of the tiled kernel for (slots per cell, source method, f = rhs (else f += rhs), HR, the forward-Euler update
+// fused into the stores (rdyhip_euler_step; always f = rhs), F -- Euler step: u_out -- stored with the non-temporal hint)
+TiledKernelFn tiled_kernel_fn(int S, int src, bool ovw, bool hr, bool euler, bool fnt) {
+  return with_flag(S == 4, [&](auto quad) { return with_flag(src != 0, [&](auto xq) { return with_flag(hr, [&](auto hr_) {
+    return with_flag(fnt, [&](auto nt) -> TiledKernelFn {
+      constexpr int s = quad ? 4 : 3, x = xq ? 1 : 0;
+      if (euler) return swe_rhs_tiled_kernel<s, x, true, hr_, true, nt>;
+      return ovw ? swe_rhs_tiled_kernel<s, x, true, hr_, false, nt> : swe_rhs_tiled_kernel<s, x, false, hr_, false, nt>;
+    });
+  }); }); });
 }
 
 using MusclKernelFn = void (*)(const KernelArgs, const MusclArgs, const double, const double *, double *);
 
-template <int S, int LIM>
-MusclKernelFn muscl_fn_lim(int src, bool ovw, bool euler) {
-  if (euler) return src ? swe_rhs_muscl_fused_kernel<S, 1, true, LIM, true> : swe_rhs_muscl_fused_kernel<S, 0, true, LIM, true>;
-  if (src) return ovw ? swe_rhs_muscl_fused_kernel<S, 1, true, LIM, false> : swe_rhs_muscl_fused_kernel<S, 1, false, LIM, false>;
-  return ovw ? swe_rhs_muscl_fused_kernel<S, 0, true, LIM, false> : swe_rhs_muscl_fused_kernel<S, 0, false, LIM, false>;
-}
-template <int S>
-MusclKernelFn muscl_fn_s(int src, bool ovw, bool euler, int limiter) {
-  switch (limiter) {
-    case RDYHIP_LIMITER_NONE: return muscl_fn_lim<S, LIMITER_NONE>(src, ovw, euler);
-    case RDYHIP_LIMITER_VANLEER: return muscl_fn_lim<S, LIMITER_VANLEER>(src, ovw, euler);
-    default: return muscl_fn_lim<S, LIMITER_MINMOD>(src, ovw, euler);
-  }
-}
+// The instantiation of the second-order kernel for (slots per cell, source method, f = rhs, the fused Euler step, limiter)
 MusclKernelFn muscl_kernel_fn(int S, int src, bool ovw, bool euler, int limiter) {
-  return S == 3 ? muscl_fn_s<3>(src, ovw, euler, limiter) : muscl_fn_s<4>(src, ovw, euler, limiter);
+  return with_flag(S == 4, [&](auto quad) { return with_flag(src != 0, [&](auto xq) {
+    auto form = [&](auto lim) -> MusclKernelFn {
+      constexpr int s = quad ? 4 : 3, x = xq ? 1 : 0;
+      if (euler) return swe_rhs_muscl_fused_kernel<s, x, true, lim, true>;
+      return ovw ? swe_rhs_muscl_fused_kernel<s, x, true, lim, false> : swe_rhs_muscl_fused_kernel<s, x, false, lim, false>;
+    };
+    switch (limiter) {
+      case RDYHIP_LIMITER_NONE: return form(std::integral_constant<int, LIMITER_NONE>());
+      case RDYHIP_LIMITER_VANLEER: return form(std::integral_constant<int, LIMITER_VANLEER>());
+      default: return form(std::integral_constant<int, LIMITER_MINMOD>());
+    }
+  }); });
 }
 
 MusclArgs muscl_args(RDyHipOperator op) {
@@ -402,12 +393,11 @@ int launch_rhs(RDyHipOperator op, int32_t phase, int32_t overwrite, int reset_di
     if (op->muscl) {
       MusclKernelFn kfn = muscl_kernel_fn(op->S, xq ? 1 : 0, overwrite != 0, euler_fused, op->config.limiter);
       hipLaunchKernelGGL(HIP_KERNEL_NAME(kfn), dim3(grid), dim3(TILE), op->lds_muscl, st, a, muscl_args(op), dt, u, f);
-    } else if (euler_fused) {
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(tiled_euler_fn(op->S, xq ? 1 : 0, op->hr, op->uout_cached)), dim3(grid), dim3(TILE), op->lds_bytes, st, a, dt, u, f);
     } else {
-      const size_t lds = op->lds_bytes;
-      const bool cached_f = (op->config.flags & RDYHIP_CONFIG_CACHED_F_STORES) != 0;
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(tiled_kernel_fn(op->S, xq ? 1 : 0, overwrite != 0, op->hr, cached_f)), dim3(grid), dim3(TILE), lds, st, a, dt, u, f);
+      // plain (cached) stores: of u_out for states that fit the Infinity Cache, of F under RDYHIP_CONFIG_CACHED_F_STORES
+      const bool     cached = euler_fused ? op->uout_cached : (op->config.flags & RDYHIP_CONFIG_CACHED_F_STORES) != 0;
+      TiledKernelFn  kfn    = tiled_kernel_fn(op->S, xq ? 1 : 0, overwrite != 0, op->hr, euler_fused, !cached);
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(kfn), dim3(grid), dim3(TILE), op->lds_bytes, st, a, dt, u, f);
     }
   } else {
     if (phase == RDYHIP_PHASE_HALO) {
@@ -1058,7 +1048,7 @@ int rdyhip_create(const RDyHipConfig *config, const RDyHipMesh *mesh, int32_t nu
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, op->device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
     int q = 0;
-    const void *kfn = (const void *)tiled_kernel_fn(S, config->source_method == RDYHIP_SOURCE_IMPLICIT_XQ2018 ? 1 : 0, true, hr_on);
+    const void *kfn = (const void *)tiled_kernel_fn(S, config->source_method == RDYHIP_SOURCE_IMPLICIT_XQ2018 ? 1 : 0, true, hr_on, false, true);
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, kfn, TILE, lds_bytes) == hipSuccess && q > 0) per_cu = q;
     if (const char *e2 = getenv("RDYHIP_BLOCKS_PER_CU")) {
       if (atoi(e2) > 0) per_cu = atoi(e2);

@@ -145,6 +145,13 @@ __device__ __forceinline__ T load_uniform(const T *p, int i) {
 // a field of the device-resident ColdArgs block: one scalar load at the point of use
 #define RDY_COLD(a, field) (load_uniform(&(a).cold->field, 0))
 
+// The workgroup's block of cells in the cell-centric kernels.  Block ids are dealt round-robin to the 8 XCDs: with
+// xcd_chunks > 0 (KernelArgs) each XCD gets a contiguous range of blocks, so concurrently running blocks are neighbours.
+// (Takes the count, not the KernelArgs: read through a reference here, it moves the kernels' code.)
+__device__ __forceinline__ int xcd_block(int xcd_chunks) {
+  return xcd_chunks > 0 ? (blockIdx.x & 7) * xcd_chunks + (blockIdx.x >> 3) : blockIdx.x;
+}
+
 __device__ __forceinline__ double wave_max(double v) {
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
@@ -156,21 +163,29 @@ __device__ __forceinline__ int wave_min(int v) {
   return v;
 }
 
-// Source terms on the in-register flux sum, then the stores of F and the
-// primitive variables.  ApplySourceSemiImplicit / ApplySourceImplicitXQ2018
-// (src/swe/swe_petsc.c:704-804, 816-932); the source reads the pre-source F
-// (src/operator.c:663).
+// Source terms of a cell on its in-register flux sum (acc1, acc2): the bed slope g h dz/dx, g h dz/dy and the friction
+// (tbx, tby) of ApplySourceSemiImplicit / ApplySourceImplicitXQ2018 (src/swe/swe_petsc.c:704-804, 816-932); the source reads
+// the pre-source F (src/operator.c:663).
 template <int SRC>
-__device__ __forceinline__ void cell_epilogue(const KernelArgs &a, int o, double dt, double h, double hu, double hv, double pu, double pv_, double acc0,
-                                              double acc1, double acc2, double dzdx, double dzdy, double n, double s0, double s1, double s2,
-                                              double *__restrict__ f) {
-  const double bedx = dzdx * GRAVITY * h;
-  const double bedy = dzdy * GRAVITY * h;
-  double       tbx = 0.0, tby = 0.0;
+__device__ __forceinline__ void cell_source(const KernelArgs &a, double dt, double h, double hu, double hv, double acc1, double acc2, double dzdx,
+                                            double dzdy, double n, double &bedx, double &bedy, double &tbx, double &tby) {
+  bedx = dzdx * GRAVITY * h;
+  bedy = dzdy * GRAVITY * h;
+  tbx = tby = 0.0;
   if (h >= a.tiny_h) {
     if (SRC == RDYHIP_SOURCE_SEMI_IMPLICIT) friction_semi_implicit(h, hu, hv, n, dt, acc1, acc2, bedx, bedy, tbx, tby);
     else friction_xq2018(h, hu, hv, n, dt, a.xq_thresh, acc1, acc2, bedx, bedy, tbx, tby);
   }
+}
+
+// F of a cell, then the stores of F and the primitive variables (the cell-centric kernel).  F is summed after the fdiv
+// stores, not taken from cell_results: computed ahead of that branch it moves the kernel's code.
+template <int SRC>
+__device__ __forceinline__ void cell_epilogue(const KernelArgs &a, int o, double dt, double h, double hu, double hv, double pu, double pv_, double acc0,
+                                              double acc1, double acc2, double dzdx, double dzdy, double n, double s0, double s1, double s2,
+                                              double *__restrict__ f) {
+  double bedx, bedy, tbx, tby;
+  cell_source<SRC>(a, dt, h, hu, hv, acc1, acc2, dzdx, dzdy, n, bedx, bedy, tbx, tby);
   if (a.fdiv) {
     a.fdiv[3 * (int64_t)o + 0] = acc0;
     a.fdiv[3 * (int64_t)o + 1] = acc1;
@@ -185,17 +200,12 @@ __device__ __forceinline__ void cell_epilogue(const KernelArgs &a, int o, double
   a.pv[3 * (int64_t)o + 2] = pv_;
 }
 
-// cell_epilogue split in two for the pipelined kernel: the arithmetic ...
+// F of a cell into out[3], for the tiled kernels (they store whole rows per wave: wave_store_rows3)
 template <int SRC>
 __device__ __forceinline__ void cell_results(const KernelArgs &a, double dt, double h, double hu, double hv, double acc0, double acc1, double acc2,
                                              double dzdx, double dzdy, double n, double s0, double s1, double s2, double *out) {
-  const double bedx = dzdx * GRAVITY * h;
-  const double bedy = dzdy * GRAVITY * h;
-  double       tbx = 0.0, tby = 0.0;
-  if (h >= a.tiny_h) {
-    if (SRC == RDYHIP_SOURCE_SEMI_IMPLICIT) friction_semi_implicit(h, hu, hv, n, dt, acc1, acc2, bedx, bedy, tbx, tby);
-    else friction_xq2018(h, hu, hv, n, dt, a.xq_thresh, acc1, acc2, bedx, bedy, tbx, tby);
-  }
+  double bedx, bedy, tbx, tby;
+  cell_source<SRC>(a, dt, h, hu, hv, acc1, acc2, dzdx, dzdy, n, bedx, bedy, tbx, tby);
   out[0] = acc0 + s0;
   out[1] = acc1 + (-bedx - tbx + s1);
   out[2] = acc2 + (-bedy - tby + s2);
@@ -337,6 +347,20 @@ constexpr uint32_t EDGE_OTHER_NEG    = 1u << 24;  // the reconstructed component
 constexpr uint32_t EDGE_NOT_OWNED    = 1u << 25;
 // slot references of a triangle mesh (S == 3): 3 x 10 bits in one uint32, 0x3FF = unused
 constexpr uint32_t REF3_EMPTY = 0x3FF;
+
+// index of slot s's edge in the tile's edge list, or -1 for an unused slot.  r0 (, r1): the cell's slot references
+// (KernelArgs::slot_ref): triangles three 10-bit ones in r0, quads four 16-bit ones in r0, r1.  (The first-order kernel's
+// phase 2 decodes inline: through this function its quad instantiations compile to other code.)
+template <int S>
+__device__ __forceinline__ int slot_edge(uint32_t r0, uint32_t r1, int s) {
+  if (S == 3) {
+    const uint32_t ref = (r0 >> (10 * s)) & 0x3FF;
+    return ref == REF3_EMPTY ? -1 : (int)ref;
+  }
+  const uint32_t w   = (s < 2) ? r0 : r1;
+  const uint32_t ref = (s & 1) ? (w >> 16) : (w & 0xFFFFu);
+  return ref == SLOT_EMPTY ? -1 : (int)ref;
+}
 
 __device__ __forceinline__ void edge_normal(uint32_t lr, double cs, double &cn, double &sn) {
   double other = rdy_sqrt(fma(-cs, cs, 1.0));
@@ -899,9 +923,7 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(3, 3))) vo
 template <int S, int SRC>
 __global__ __launch_bounds__(BLOCK) void swe_rhs_kernel(const KernelArgs a, const double dt, const double *__restrict__ u,
                                                         double *__restrict__ f) {
-  int tile = blockIdx.x;
-  if (a.xcd_chunks > 0) tile = (blockIdx.x & 7) * a.xcd_chunks + (blockIdx.x >> 3);
-  const int i = tile * BLOCK + threadIdx.x;
+  const int i = xcd_block(a.xcd_chunks) * BLOCK + threadIdx.x;
 
   double best      = 0.0;  // largest Courant number seen by this thread (> 0 only)
   int    best_slot = -1;
