@@ -146,7 +146,8 @@ typedef struct RDyHipOperator_s *RDyHipOperator;
  * in place; see rdyhip_field_ptr() */
 typedef enum {
   RDYHIP_FIELD_PRIMITIVE_VARIABLES = 0, /* Operator.primitive_variables [owned][3] (h,u,v); out */
-  RDYHIP_FIELD_EXTERNAL_SOURCES    = 1, /* Operator.petsc.external_sources [owned][3]; in; also src_inst */
+  RDYHIP_FIELD_EXTERNAL_SOURCES    = 1, /* Operator.petsc.external_sources [owned][3]; in; also src_inst.  Read-only users
+                                           take it through rdyhip_field_ptr_const (see "the water-source plane" below) */
   RDYHIP_FIELD_MANNINGS            = 2, /* Operator.petsc.material_properties [owned][1]; in */
   RDYHIP_FIELD_FLUX_DIVERGENCE     = 3, /* Operator.flux_divergence [owned][3]; out, only if enabled */
   RDYHIP_FIELD_GRADIENTS           = 4, /* second order: InteriorFluxOperator.grad_h/grad_hu/grad_hv interleaved,
@@ -240,7 +241,24 @@ int rdyhip_reset_boundary_fluxes_accum(RDyHipOperator op);
 /* Get/RestoreOperator{Regional,Domain}ExternalSource (include/private/rdyoperatorimpl.h:258-261,
  *   src/operator.c:1203-1241,1394-1429) as used by RDySet{Regional,Domain}{Water,XMomentum,YMomentum}Source
  *   (src/rdydata.c:225-366): sets component `comp` of the external source of
- *   `n` owned cells; owned_cell_ids == NULL means owned cells 0..n-1 (domain). Host pointers. */
+ *   `n` owned cells; owned_cell_ids == NULL means owned cells 0..n-1 (domain). Host pointers.
+ *
+ * The water-source plane.  The momentum sources (components 1 and 2) are zero-initialised at create (src/operator.c:91-129)
+ * and most runs never set them.  While that is known to hold, the first-order and hydrostatic-reconstruction kernels read the
+ * water source from a dense [owned] mirror of component 0 that the library keeps beside the canonical [owned][3] array: 8 B
+ * of memory traffic per cell instead of 24.  "Known" means: every write of the source so far went through a call that lets
+ * the host see it.
+ *   - comp 0, any setter below (this one, _on, rdyhip_forcing_fill_source / _gather_source): written to both arrays.
+ *   - comp 1 / 2 with host values (this one, _on) or a host scalar (fill_source): the values are scanned; anything whose
+ *     bit pattern is not that of +0.0 (-0.0 and NaN included) ends the mode.  gather_source on comp 1 / 2 ends it unseen.
+ *   - rdyhip_refresh_field from a HOST array: momentum entries all +0.0 -> the plane is rewritten and the mode (re)starts;
+ *     this is the only way back into it.  Otherwise it ends.  From a DEVICE array: the mode ends (the call must not block,
+ *     so the host cannot look).
+ *   - rdyhip_field_ptr(RDYHIP_FIELD_EXTERNAL_SOURCES): the caller may write the array in place, so the mode ends for the
+ *     life of the operator.  rdyhip_field_ptr_const hands out the same pointer for reading and changes nothing.
+ * Outside the mode the kernels read the [owned][3] array as before; the results are the same bits either way, and the
+ * [owned][3] array is current at all times.  The mode is read when a launch is enqueued: launches and setters on one stream
+ * stay consistent, across streams the caller orders them as for the data.  rdyhip_source_is_water_only reports it. */
 int rdyhip_set_external_source(RDyHipOperator op, int32_t comp, int32_t n, const int32_t *owned_cell_ids, const double *values);
 
 /* Get/RestoreOperator{Regional,Domain}MaterialProperties (rdyoperatorimpl.h:263-266)
@@ -299,6 +317,14 @@ int rdyhip_forcing_nearest_map(int32_t n, const double *d_xc, const double *d_yc
  * kernel can write the external source on the GPU, an output routine can read
  * primitive_variables (read by src/rdyadvance.c's averaging monitors). */
 int rdyhip_field_ptr(RDyHipOperator op, RDyHipField field, double **device_ptr, int64_t *num_values);
+/* The same pointer for readers (output monitors of primitive_variables or the source): nothing is assumed to be written.
+ * rdyhip_field_ptr(RDYHIP_FIELD_EXTERNAL_SOURCES) on the other hand hands out a pointer that MAY be written in place, which ends
+ * the water-only mode of the source for good (see rdyhip_set_external_source). */
+int rdyhip_field_ptr_const(RDyHipOperator op, RDyHipField field, const double **device_ptr, int64_t *num_values);
+/* *out = 1 while the kernels read the water source from its own plane (see rdyhip_set_external_source), else 0 */
+int rdyhip_source_is_water_only(RDyHipOperator op, int32_t *out);
+/* A device array of external sources ends the water-only mode of the source: this call does not block, so the host cannot
+ * look at the momentum entries (keeping the plane on this path is a follow-up).  A host array keeps or restarts it. */
 int rdyhip_refresh_field(RDyHipOperator op, RDyHipField field, const double *values, int64_t num_values, int32_t values_on_device, void *stream);
 /* keep Operator.flux_divergence (one extra [owned][3] store per apply); off by default */
 int rdyhip_enable_flux_divergence(RDyHipOperator op, int32_t enable);
@@ -492,7 +518,9 @@ typedef struct {
   int64_t num_edge_records;   /* sum of the tiles' edge lists (cut edges appear in two tiles) */
   int32_t owned_is_prefix;    /* 1 if owned cell o is local cell o */
   int64_t device_bytes;       /* bytes of device memory held by the operator */
-  int64_t bytes_per_apply;    /* bytes one full apply must move (layout-exact, not the 176 B/cell model) */
+  int64_t bytes_per_apply;    /* bytes one full apply must move (layout-exact, not the 176 B/cell model); a create-time figure and
+                                 an upper bound: it counts 24 B per cell for the external source, of which the first-order / HR
+                                 kernels read 8 B while the source is water only (rdyhip_source_is_water_only) */
   int32_t second_order_fused; /* 1 for a second-order operator: the gradients are formed in LDS by the flux kernel, only
                                  rdyhip_compute_gradients(RDYHIP_PHASE_HALO) is needed before the gradient exchange (the
                                  two-launch form of rounds 1-4 is gone); 0: first order */

@@ -140,6 +140,12 @@ struct RDyHipOperator_s {
 
   DevBuf<int32_t> d_o2l, d_nbr, d_pos, d_halo_list, d_btype, d_bleft, d_bghost_list;
   DevBuf<double>  d_cn, d_sn, d_coef, d_dzdx, d_dzdy, d_mannings, d_extsrc;
+  // The water source by itself, [n_owned]: a mirror of component 0 of d_extsrc (which stays the canonical array and is always
+  // current), kept by every writer of the source while src_water_only holds.  The first-order / HR tiled kernels then read
+  // it instead of the 24-B rows: 8 B of HBM traffic per cell where a read of any part of a row costs all 24.
+  DevBuf<double>  d_src_water;
+  bool            src_water_only = true;   // every momentum source is +0.0 and the plane is current
+  bool            src_escaped    = false;  // rdyhip_field_ptr handed out d_extsrc: it may be written behind our back, for good
   DevBuf<double>  d_bvalues, d_bflux, d_baccum, d_bcn, d_bsn, d_pv, d_fdiv, d_blk_max;
   DevBuf<int32_t> d_blk_pos;
   DevBuf<DeviceCourant> d_courant;
@@ -189,7 +195,7 @@ struct RDyHipOperator_s {
   ~RDyHipOperator_s() {
     d_o2l.release(); d_nbr.release(); d_pos.release(); d_halo_list.release(); d_btype.release(); d_bleft.release();
     d_bghost_list.release(); d_cn.release(); d_sn.release(); d_coef.release(); d_dzdx.release(); d_dzdy.release();
-    d_mannings.release(); d_extsrc.release(); d_bvalues.release(); d_bflux.release();
+    d_mannings.release(); d_extsrc.release(); d_src_water.release(); d_bvalues.release(); d_bflux.release();
     d_baccum.release(); d_bcn.release(); d_bsn.release(); d_pv.release(); d_fdiv.release(); d_blk_max.release();
     d_blk_pos.release(); d_courant.release(); d_cold.release(); d_stage_vals.release(); d_stage_ids.release(); d_scratch_f.release();
     d_tiles.release(); d_e_lr.release(); d_e_pos.release(); d_x_lr.release(); d_x_flags.release(); d_x_cs.release(); d_x_cfac.release(); d_x_mid.release();
@@ -330,6 +336,7 @@ int launch_rhs(RDyHipOperator op, int32_t phase, int32_t overwrite, int reset_di
   a.dzdy       = op->d_dzdy.p;
   a.mannings   = op->d_mannings.p;
   a.extsrc     = op->d_extsrc.p;
+  a.src_mom    = 1;
   a.pv         = op->d_pv.p;
   a.fdiv       = op->keep_fdiv ? op->d_fdiv.p : nullptr;
   a.n_buckets  = (int32_t)op->d_blk_max.n;
@@ -397,6 +404,11 @@ int launch_rhs(RDyHipOperator op, int32_t phase, int32_t overwrite, int reset_di
       // plain (cached) stores: of u_out for states that fit the Infinity Cache, of F under RDYHIP_CONFIG_CACHED_F_STORES
       const bool     cached = euler_fused ? op->uout_cached : (op->config.flags & RDYHIP_CONFIG_CACHED_F_STORES) != 0;
       TiledKernelFn  kfn    = tiled_kernel_fn(op->S, xq ? 1 : 0, overwrite != 0, op->hr, euler_fused, !cached);
+      // the flag is read here, when the launch is enqueued: launches and source writers on one stream stay consistent
+      if (op->src_water_only) {
+        a.extsrc  = op->d_src_water.p;
+        a.src_mom = 0;
+      }
       hipLaunchKernelGGL(HIP_KERNEL_NAME(kfn), dim3(grid), dim3(TILE), op->lds_bytes, st, a, dt, u, f);
     }
   } else {
@@ -1148,6 +1160,7 @@ int rdyhip_create(const RDyHipConfig *config, const RDyHipMesh *mesh, int32_t nu
   }
   TRY_RC(op->d_mannings.zeros((size_t)no));
   TRY_RC(op->d_extsrc.zeros((size_t)3 * no));
+  TRY_RC(op->d_src_water.zeros((size_t)no));
   TRY_RC(op->d_bvalues.zeros((size_t)3 * K));
   TRY_RC(op->d_bflux.zeros((size_t)3 * K));
   TRY_RC(op->d_baccum.zeros((size_t)3 * K));
@@ -1181,7 +1194,7 @@ int rdyhip_create(const RDyHipConfig *config, const RDyHipMesh *mesh, int32_t nu
   if (mesh->edge_global_ids) op->h_edge_gid.assign(mesh->edge_global_ids, mesh->edge_global_ids + ne);
 
   op->device_bytes = op->d_o2l.bytes() + op->d_nbr.bytes() + op->d_pos.bytes() + op->d_cn.bytes() + op->d_sn.bytes() + op->d_coef.bytes() +
-                     op->d_dzdx.bytes() + op->d_dzdy.bytes() + op->d_mannings.bytes() + op->d_extsrc.bytes() +
+                     op->d_dzdx.bytes() + op->d_dzdy.bytes() + op->d_mannings.bytes() + op->d_extsrc.bytes() + op->d_src_water.bytes() +
                      op->d_pv.bytes() + op->d_bvalues.bytes() + op->d_bflux.bytes() + op->d_baccum.bytes() + op->d_blk_max.bytes() +
                      op->d_blk_pos.bytes() + op->d_tiles.bytes() + op->d_e_lr.bytes() + op->d_e_pos.bytes() + op->d_hcells.bytes() + op->d_tile_bk.bytes() + op->d_tile_boff.bytes() +
                      op->d_e_cs.bytes() + op->d_slot_ref.bytes() + op->d_slot_ref3.bytes() + op->d_grad.bytes() + op->d_e_mid.bytes() +
@@ -1279,7 +1292,9 @@ int rdyhip_reset_boundary_fluxes_accum(RDyHipOperator op) {
   return 0;
 }
 
-static int scatter_component(RDyHipOperator op, double *dst, int ncomp, int comp, int32_t n, const int32_t *ids, const double *values) {
+// `mirror`: a second destination [n_owned] that receives the same staged values (the water-source plane), or nullptr
+static int scatter_component(RDyHipOperator op, double *dst, int ncomp, int comp, int32_t n, const int32_t *ids, const double *values,
+                             double *mirror = nullptr) {
   if (n < 0 || n > op->n_owned) return fail(RDYHIP_ERR_ARG_SIZ, "n (%d) exceeds the number of owned cells (%d)", n, op->n_owned);
   if (n == 0) return 0;
   if (!values) return fail(RDYHIP_ERR_USER, "null values");
@@ -1306,14 +1321,39 @@ static int scatter_component(RDyHipOperator op, double *dst, int ncomp, int comp
   }
   hipLaunchKernelGGL(scatter_component_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, n, dids, op->d_stage_vals.p, dst, ncomp, comp);
   HIP_TRY(hipGetLastError());
+  if (mirror) {
+    hipLaunchKernelGGL(scatter_component_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, n, dids, op->d_stage_vals.p, mirror, 1, 0);
+    HIP_TRY(hipGetLastError());
+  }
   HIP_TRY(hipDeviceSynchronize());
   return 0;
+}
+
+// ---- the water-source plane (RDyHipOperator_s::d_src_water) -----------------------------------------------------------
+// +0.0 and nothing else: -0.0 and NaN count as a momentum source
+static bool is_plus_zero(double v) {
+  uint64_t bits;
+  memcpy(&bits, &v, sizeof(bits));
+  return bits == 0;
+}
+static bool all_plus_zero(const double *v, int64_t n, int64_t step = 1) {
+  for (int64_t i = 0; i < n; ++i)
+    if (!is_plus_zero(v[i * step])) return false;
+  return true;
+}
+// A host-side writer of source component `comp` (arguments already checked by the caller's scatter): momentum values other
+// than +0.0 end the water-only mode (no data moves: d_extsrc is always current).  Returns the plane if this write has to go
+// into it as well, else nullptr.
+static double *source_mirror(RDyHipOperator op, int comp, int32_t n, const double *values) {
+  if (comp == 0) return op->src_water_only ? op->d_src_water.p : nullptr;
+  if (op->src_water_only && n > 0 && n <= op->n_owned && values && !all_plus_zero(values, n)) op->src_water_only = false;
+  return nullptr;
 }
 
 int rdyhip_set_external_source(RDyHipOperator op, int32_t comp, int32_t n, const int32_t *owned_cell_ids, const double *values) {
   if (!op) return fail(RDYHIP_ERR_USER, "null operator");
   if (comp < 0 || comp > 2) return fail(RDYHIP_ERR_USER, "bad source component %d", comp);
-  return scatter_component(op, op->d_extsrc.p, 3, comp, n, owned_cell_ids, values);
+  return scatter_component(op, op->d_extsrc.p, 3, comp, n, owned_cell_ids, values, source_mirror(op, comp, n, values));
 }
 
 int rdyhip_set_mannings(RDyHipOperator op, int32_t n, const int32_t *owned_cell_ids, const double *values) {
@@ -1394,7 +1434,8 @@ static int stage_release(StageRing::Slot *s, hipStream_t st) {
   return 0;
 }
 
-static int scatter_component_on(RDyHipOperator op, double *dst, int ncomp, int comp, int32_t n, const int32_t *ids, const double *values, hipStream_t st) {
+static int scatter_component_on(RDyHipOperator op, double *dst, int ncomp, int comp, int32_t n, const int32_t *ids, const double *values, hipStream_t st,
+                                double *mirror = nullptr) {
   if (n < 0 || n > op->n_owned) return fail(RDYHIP_ERR_ARG_SIZ, "n (%d) exceeds the number of owned cells (%d)", n, op->n_owned);
   if (n == 0) return 0;
   if (!values) return fail(RDYHIP_ERR_USER, "null values");
@@ -1413,13 +1454,17 @@ static int scatter_component_on(RDyHipOperator op, double *dst, int ncomp, int c
   const int32_t *dids = ids ? (const int32_t *)((const char *)s->d + vbytes) : nullptr;
   hipLaunchKernelGGL(scatter_component_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, dids, (const double *)s->d, dst, ncomp, comp);
   HIP_TRY(hipGetLastError());
+  if (mirror) {
+    hipLaunchKernelGGL(scatter_component_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, dids, (const double *)s->d, mirror, 1, 0);
+    HIP_TRY(hipGetLastError());
+  }
   return stage_release(s, st);
 }
 
 int rdyhip_set_external_source_on(RDyHipOperator op, int32_t comp, int32_t n, const int32_t *owned_cell_ids, const double *values, void *stream) {
   if (!op) return fail(RDYHIP_ERR_USER, "null operator");
   if (comp < 0 || comp > 2) return fail(RDYHIP_ERR_USER, "bad source component %d", comp);
-  return scatter_component_on(op, op->d_extsrc.p, 3, comp, n, owned_cell_ids, values, (hipStream_t)stream);
+  return scatter_component_on(op, op->d_extsrc.p, 3, comp, n, owned_cell_ids, values, (hipStream_t)stream, source_mirror(op, comp, n, values));
 }
 
 int rdyhip_set_mannings_on(RDyHipOperator op, int32_t n, const int32_t *owned_cell_ids, const double *values, void *stream) {
@@ -1453,22 +1498,33 @@ int rdyhip_set_boundary_values_on(RDyHipOperator op, int32_t boundary, int32_t c
   return stage_release(s, st);
 }
 
+static int field_ptr_internal(RDyHipOperator op, RDyHipField field, double **device_ptr, int64_t *num_values);
+
 int rdyhip_refresh_field(RDyHipOperator op, RDyHipField field, const double *values, int64_t num_values, int32_t values_on_device, void *stream) {
   if (!op) return fail(RDYHIP_ERR_USER, "null operator");
   double *dst = nullptr;
   int64_t n   = 0;
   if (field != RDYHIP_FIELD_EXTERNAL_SOURCES && field != RDYHIP_FIELD_MANNINGS)
     return fail(RDYHIP_ERR_USER, "rdyhip_refresh_field: only the operator's input fields (external sources, Manning n) can be written");
-  int rc = rdyhip_field_ptr(op, field, &dst, &n);
+  int rc = field_ptr_internal(op, field, &dst, &n);
   if (rc) return rc;
   if (num_values != n) return fail(RDYHIP_ERR_ARG_SIZ, "%lld values for a device field of %lld", (long long)num_values, (long long)n);
   if (n == 0) return 0;
   if (!values) return fail(RDYHIP_ERR_USER, "null values");
   hipStream_t  st = (hipStream_t)stream;
   const size_t bytes = sizeof(double) * (size_t)n;
+  const bool   source = field == RDYHIP_FIELD_EXTERNAL_SOURCES;
   if (values_on_device) {
+    // this path must not block, so the host cannot look at the momentum entries: the kernels read the [owned][3] array from here on
+    if (source) op->src_water_only = false;
     HIP_TRY(hipMemcpyAsync(dst, values, bytes, hipMemcpyDeviceToDevice, st));
     return 0;
+  }
+  // the only way back into the water-only mode: a whole host array whose momentum entries are all +0.0
+  bool plane = false;
+  if (source) {
+    plane = !op->src_escaped && all_plus_zero(values + 1, op->n_owned, 3) && all_plus_zero(values + 2, op->n_owned, 3);
+    op->src_water_only = plane;
   }
   StageRing::Slot *s;
   rc = stage_acquire(op, bytes, &s);
@@ -1477,6 +1533,9 @@ int rdyhip_refresh_field(RDyHipOperator op, RDyHipField field, const double *val
   if (!rc) rc = stage_ready(op, s, st);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(dst, s->d, bytes, hipMemcpyDeviceToDevice, st));
+  // the whole plane from the staged copy: component 0 of every row, 8 B wide at a source pitch of 24 B
+  if (plane)
+    HIP_TRY(hipMemcpy2DAsync(op->d_src_water.p, sizeof(double), s->d, 3 * sizeof(double), sizeof(double), (size_t)op->n_owned, hipMemcpyDeviceToDevice, st));
   return stage_release(s, st);
 }
 
@@ -1495,6 +1554,12 @@ int rdyhip_forcing_fill_source(RDyHipOperator op, int32_t comp, int32_t n, const
   if (rc || n == 0) return rc;
   hipLaunchKernelGGL(forcing_fill_kernel, dim3(forcing_grid(n)), dim3(256), 0, (hipStream_t)stream, n, d_owned_cell_ids, value, op->d_extsrc.p, 3, comp);
   HIP_TRY(hipGetLastError());
+  if (comp != 0) {
+    if (!is_plus_zero(value)) op->src_water_only = false;
+  } else if (op->src_water_only) {
+    hipLaunchKernelGGL(forcing_fill_kernel, dim3(forcing_grid(n)), dim3(256), 0, (hipStream_t)stream, n, d_owned_cell_ids, value, op->d_src_water.p, 1, 0);
+    HIP_TRY(hipGetLastError());
+  }
   return 0;
 }
 
@@ -1504,13 +1569,20 @@ int rdyhip_forcing_gather_source(RDyHipOperator op, int32_t comp, int32_t n, con
   if (rc || n == 0) return rc;
   if (!d_data || !d_data2mesh_idx) return fail(RDYHIP_ERR_USER, "null dataset or map");
   if (stride < 1 || offset < 0) return fail(RDYHIP_ERR_USER, "bad stride/offset (%lld, %lld)", (long long)stride, (long long)offset);
-  if (scale == 1.0)
-    hipLaunchKernelGGL(forcing_gather_kernel<false>, dim3(forcing_grid(n)), dim3(256), 0, (hipStream_t)stream, n, d_owned_cell_ids, d_data,
-                       d_data2mesh_idx, stride, offset, scale, op->d_extsrc.p, 3, comp);
-  else
-    hipLaunchKernelGGL(forcing_gather_kernel<true>, dim3(forcing_grid(n)), dim3(256), 0, (hipStream_t)stream, n, d_owned_cell_ids, d_data,
-                       d_data2mesh_idx, stride, offset, scale, op->d_extsrc.p, 3, comp);
-  HIP_TRY(hipGetLastError());
+  // the values are the device's: a momentum component ends the water-only mode without a look; the water component goes
+  // into the [owned][3] array and, in that mode, into the plane as well (same kernel, same operands: the same bits)
+  if (comp != 0) op->src_water_only = false;
+  double *const dsts[2] = {op->d_extsrc.p, comp == 0 && op->src_water_only ? op->d_src_water.p : nullptr};
+  for (int k = 0; k < 2 && dsts[k]; ++k) {
+    const int ncomp = k == 0 ? 3 : 1;
+    if (scale == 1.0)
+      hipLaunchKernelGGL(forcing_gather_kernel<false>, dim3(forcing_grid(n)), dim3(256), 0, (hipStream_t)stream, n, d_owned_cell_ids, d_data,
+                         d_data2mesh_idx, stride, offset, scale, dsts[k], ncomp, comp);
+    else
+      hipLaunchKernelGGL(forcing_gather_kernel<true>, dim3(forcing_grid(n)), dim3(256), 0, (hipStream_t)stream, n, d_owned_cell_ids, d_data,
+                         d_data2mesh_idx, stride, offset, scale, dsts[k], ncomp, comp);
+    HIP_TRY(hipGetLastError());
+  }
   return 0;
 }
 
@@ -1556,7 +1628,8 @@ int rdyhip_forcing_nearest_map(int32_t n, const double *d_xc, const double *d_yc
   return 0;
 }
 
-int rdyhip_field_ptr(RDyHipOperator op, RDyHipField field, double **device_ptr, int64_t *num_values) {
+// rdyhip_field_ptr without its side effect on the external source (the pointer does not leave the library, or leaves it const)
+static int field_ptr_internal(RDyHipOperator op, RDyHipField field, double **device_ptr, int64_t *num_values) {
   if (!op || !device_ptr) return fail(RDYHIP_ERR_USER, "null argument");
   int64_t n = 0;
   switch (field) {
@@ -1576,6 +1649,31 @@ int rdyhip_field_ptr(RDyHipOperator op, RDyHipField field, double **device_ptr, 
     default: return fail(RDYHIP_ERR_USER, "unknown field %d", (int)field);
   }
   if (num_values) *num_values = n;
+  return 0;
+}
+
+int rdyhip_field_ptr(RDyHipOperator op, RDyHipField field, double **device_ptr, int64_t *num_values) {
+  int rc = field_ptr_internal(op, field, device_ptr, num_values);
+  if (rc) return rc;
+  if (field == RDYHIP_FIELD_EXTERNAL_SOURCES) {
+    // the caller may write the array in place at any time from now on: the water plane cannot be kept, for good
+    op->src_escaped    = true;
+    op->src_water_only = false;
+  }
+  return 0;
+}
+
+int rdyhip_field_ptr_const(RDyHipOperator op, RDyHipField field, const double **device_ptr, int64_t *num_values) {
+  double *p = nullptr;
+  int     rc = field_ptr_internal(op, field, device_ptr ? &p : nullptr, num_values);
+  if (rc) return rc;
+  *device_ptr = p;
+  return 0;
+}
+
+int rdyhip_source_is_water_only(RDyHipOperator op, int32_t *out) {
+  if (!op || !out) return fail(RDYHIP_ERR_USER, "null argument");
+  *out = op->src_water_only ? 1 : 0;
   return 0;
 }
 

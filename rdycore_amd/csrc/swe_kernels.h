@@ -111,7 +111,7 @@ struct KernelArgs {
   const double  *coef;       // [S][stride]
   const double  *dzdx, *dzdy;  // [n_owned]
   const double  *mannings;   // [n_owned]
-  const double  *extsrc;     // [n_owned][3]
+  const double  *extsrc;     // src_mom = 1: [n_owned][3]; src_mom = 0: [n_owned], the water component alone
   double        *pv;         // [n_owned][3]
   double        *fdiv;       // [n_owned][3] or nullptr
   double        *u_out;      // EULER kernels: [num_cells][3] state after the step, owned rows written (u_out = u + dt F)
@@ -123,6 +123,9 @@ struct KernelArgs {
   int32_t        phase;      // RDYHIP_PHASE_*
   int32_t        overwrite;  // 1: f = rhs, 0: f += rhs
   int32_t        xcd_chunks; // >0: blocks are dealt to XCDs in contiguous chunks of this many tiles
+  int32_t        src_mom;    // first-order / HR tiled kernel: 1: extsrc holds all three source components; 0: extsrc is the dense
+                             // water-source plane and the momentum sources are zero (launch_rhs).  The other kernels always get
+                             // the [n_owned][3] array and do not look.  (Sits in what was padding: the struct does not grow.)
   // ---- tiled kernel only
   const struct TileDesc *tiles;  // [ntiles+1]
   const uint32_t *e_lr;      // [nrec] packed LDS slots of the edge's cells
@@ -438,9 +441,13 @@ __device__ __forceinline__ void load_streams(const KernelArgs &a, int o, bool ac
       c.dzdy = RDY_LD(&a.dzdy[o]);
     }
     c.nman = RDY_LD(&a.mannings[o]);
-    c.s0   = RDY_LD(&a.extsrc[3 * (int64_t)o + 0]);
-    c.s1   = RDY_LD(&a.extsrc[3 * (int64_t)o + 1]);
-    c.s2   = RDY_LD(&a.extsrc[3 * (int64_t)o + 2]);
+    // the water source: row o of the [owned][3] array, or entry o of the water plane, which costs 8 B of HBM traffic per cell
+    // instead of the 24 B that any read of a 24-B row does
+    c.s0 = RDY_LD(&a.extsrc[a.src_mom ? 3 * (int64_t)o : (int64_t)o]);
+    if (a.src_mom) {  // wave-uniform; otherwise the momentum sources stay the zeros set above
+      c.s1 = RDY_LD(&a.extsrc[3 * (int64_t)o + 1]);
+      c.s2 = RDY_LD(&a.extsrc[3 * (int64_t)o + 2]);
+    }
   }
 }
 

@@ -311,6 +311,13 @@ class Operator:
     def external_sources(self) -> torch.Tensor:
         return self._field(1, 3)
 
+    def source_is_water_only(self) -> bool:
+        """rdyhip_source_is_water_only: the first-order / HR kernels read the water source from its own [owned] plane (every
+        momentum source is known to be +0.0).  Reading `external_sources` hands out a writable pointer and ends that for good."""
+        out = C.c_int32()
+        _lib.check(_lib.load().rdyhip_source_is_water_only(self._h, C.byref(out)))
+        return bool(out.value)
+
     @property
     def mannings_n(self) -> torch.Tensor:
         return self._field(2, 1)
