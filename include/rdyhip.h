@@ -145,7 +145,8 @@ typedef struct RDyHipOperator_s *RDyHipOperator;
 /* device-resident operator fields that may be read (or, for inputs, written)
  * in place; see rdyhip_field_ptr() */
 typedef enum {
-  RDYHIP_FIELD_PRIMITIVE_VARIABLES = 0, /* Operator.primitive_variables [owned][3] (h,u,v); out */
+  RDYHIP_FIELD_PRIMITIVE_VARIABLES = 0, /* Operator.primitive_variables [owned][3] (h,u,v); out.  Stored by the evaluations from the
+                                           first rdyhip_field_ptr / _const for it until rdyhip_field_release (see there) */
   RDYHIP_FIELD_EXTERNAL_SOURCES    = 1, /* Operator.petsc.external_sources [owned][3]; in; also src_inst.  Read-only users
                                            take it through rdyhip_field_ptr_const (see "the water-source plane" below) */
   RDYHIP_FIELD_MANNINGS            = 2, /* Operator.petsc.material_properties [owned][1]; in */
@@ -317,6 +318,29 @@ int rdyhip_forcing_nearest_map(int32_t n, const double *d_xc, const double *d_yc
  * kernel can write the external source on the GPU, an output routine can read
  * primitive_variables (read by src/rdyadvance.c's averaging monitors). */
 int rdyhip_field_ptr(RDyHipOperator op, RDyHipField field, double **device_ptr, int64_t *num_values);
+/* Primitive variables on demand.  (h, u, v) of a cell are a function of its own state alone, and in the reference only the
+ * output monitors read them, when primitive-variable output is configured (src/rdysetup.c:1535).  So the evaluations
+ * (rdyhip_apply / _rhs_function / _apply_phase / _euler_step and the _overlapped forms) store them only once somebody can look:
+ *   - A pointer obtained through rdyhip_field_ptr or rdyhip_field_ptr_const(RDYHIP_FIELD_PRIMITIVE_VARIABLES) is written by every
+ *     evaluation from then on, until rdyhip_field_release: what every evaluation did before this became optional.  A host that
+ *     asks once at setup sees no difference.
+ *   - A host that never asks pays nothing: 24 B per cell of stores less in every launch.
+ *   - The first request after evaluations that did not store fills ALL owned rows from the u_local array of the most recent of
+ *     them (for rdyhip_euler_step: its INPUT state), with the arithmetic of the kernels (the same bits a storing launch writes),
+ *     enqueued on the stream that evaluation was given.  That array must still exist and still hold that state when the request
+ *     is made: in RDycore it does (u_local is rewritten only by the next RHS's DMGlobalToLocal).  The library checks that the
+ *     pointer is still device memory of the operator's device and otherwise returns RDYHIP_ERR_USER without launching anything
+ *     (storing is on from then on, the next evaluation writes the array); an array that was overwritten, or freed and
+ *     allocated again, since cannot be told -- the values are then those of whatever it holds.
+ *   - Before any evaluation the array holds the zeros of rdyhip_create.
+ * Whether a launch stores is decided when it is enqueued, like the water-only mode of the source.
+ *
+ * rdyhip_field_release(RDYHIP_FIELD_PRIMITIVE_VARIABLES): the caller will not read through pointers obtained earlier until it
+ * asks again; evaluations stop storing and the next request fills.  For a host whose output monitor fires every N steps: ask
+ * per output, read, release.  Every other field: RDYHIP_ERR_USER.
+ * rdyhip_primitive_variables_stored: *out = 1 while evaluations store them, else 0. */
+int rdyhip_field_release(RDyHipOperator op, RDyHipField field);
+int rdyhip_primitive_variables_stored(RDyHipOperator op, int32_t *out);
 /* The same pointer for readers (output monitors of primitive_variables or the source): nothing is assumed to be written.
  * rdyhip_field_ptr(RDYHIP_FIELD_EXTERNAL_SOURCES) on the other hand hands out a pointer that MAY be written in place, which ends
  * the water-only mode of the source for good (see rdyhip_set_external_source). */

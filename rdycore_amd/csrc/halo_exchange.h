@@ -208,7 +208,7 @@ int step_in_order(RDyHipOperator op, RDyHipHalo h, double dt, double *u, double 
 int step_two_streams(RDyHipOperator op, RDyHipHalo h, double dt, double *u, double *f, double *u_out, hipStream_t st) {
   const bool conc = h->halo_concurrent && (!u_out || op->use_tiled);  // (the cell kernel's separate Euler update reads all of F)
   auto part = [&](int32_t phase, int reset, bool ready) -> int {
-    if (conc && phase == RDYHIP_PHASE_HALO) return launch_rhs(op, phase, 1, 1, dt, u, f, h->cs, ready, u_out, 2);
+    if (conc && phase == RDYHIP_PHASE_HALO) return launch_rhs(op, phase, 1, 1, dt, u, f, h->cs, ready, u_out, 2, &st);
     if (reset && phase == RDYHIP_PHASE_HALO && (op->use_tiled ? op->n_halo_tiles == 0 : op->n_halo == 0)) {
       const int rc = rdyhip_reset_diagnostics(op, (void *)st);
       if (rc) return rc;

@@ -660,7 +660,7 @@ __global__ __launch_bounds__(TILE) void swe_rhs_muscl_fused_kernel(const KernelA
       const int     ncell = td.nc() - (tid - lane);  // the wave's cells of this tile
       if (a.fdiv) wave_store_rows3(a.fdiv, base, lane, ncell, acc0, acc1, acc2);
       if (!EULER || f) wave_store_rows3(f, base, lane, ncell, res[0], res[1], res[2]);
-      wave_store_rows3(a.pv, base, lane, ncell, h, pu, pv_);
+      if (a.pv) wave_store_rows3(a.pv, base, lane, ncell, h, pu, pv_);  // once somebody has asked for them (KernelArgs::pv)
       if (EULER) {  // rdyhip_euler_step: the forward-Euler update rides on the stores, F only if asked for
         const double n0 = h + dt * res[0], n1 = hu + dt * res[1], n2 = hv + dt * res[2];
         if (!a.o2l) {

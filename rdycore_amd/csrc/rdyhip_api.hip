@@ -147,6 +147,12 @@ struct RDyHipOperator_s {
   bool            src_water_only = true;   // every momentum source is +0.0 and the plane is current
   bool            src_escaped    = false;  // rdyhip_field_ptr handed out d_extsrc: it may be written behind our back, for good
   DevBuf<double>  d_bvalues, d_bflux, d_baccum, d_bcn, d_bsn, d_pv, d_fdiv, d_blk_max;
+  // The primitive variables are stored by the evaluations only once somebody can look at them (rdyhip_field_ptr, until
+  // rdyhip_field_release); the first request after evaluations that did not store derives them from the state of the last one.
+  bool            pv_wanted  = false;    // d_pv has been handed out: every launch stores
+  bool            pv_pending = false;    // at least one evaluation since the last store did not store
+  const double   *pv_u       = nullptr;  // u_local of the most recent evaluation that did not store ...
+  hipStream_t     pv_stream  = nullptr;  // ... and the caller's stream it was enqueued on
   DevBuf<int32_t> d_blk_pos;
   DevBuf<DeviceCourant> d_courant;
   DevBuf<ColdArgs>      d_cold;   // the kernels' rarely read pointers (swe_kernels.h), written once at create
@@ -302,7 +308,8 @@ int launch_gradients(RDyHipOperator op, int32_t phase, const double *u, hipStrea
 // ordinary launch); 1 / 2: the first / second half, for the interior and the halo launch of rdyhip_rhs_overlapped, which
 // run side by side on two streams and must not share a bucket
 int launch_rhs(RDyHipOperator op, int32_t phase, int32_t overwrite, int reset_diag, double dt, const double *u, double *f, hipStream_t st,
-               bool gradients_ready = false, double *u_out = nullptr, int bucket_half = 0) {
+               bool gradients_ready = false, double *u_out = nullptr, int bucket_half = 0, const hipStream_t *joined_on = nullptr) {
+  // joined_on: the caller's stream, where `st` is the library's exchange stream (the halo launch of a two-stream step)
   if (!op) return fail(RDYHIP_ERR_USER, "null operator");
   // an Euler-step launch rewrites the attached halo's send buffer (tiles flagged TILE_SEND_FLAG): whatever it held is gone
   // (rdyhip_euler_step_overlapped notes the new content itself once its launches are enqueued)
@@ -337,7 +344,14 @@ int launch_rhs(RDyHipOperator op, int32_t phase, int32_t overwrite, int reset_di
   a.mannings   = op->d_mannings.p;
   a.extsrc     = op->d_extsrc.p;
   a.src_mom    = 1;
-  a.pv         = op->d_pv.p;
+  // read here, when the launch is enqueued (like src_water_only below).  Not stored: the request that comes later derives
+  // them from this launch's input state, on the stream the caller ordered it on
+  a.pv         = op->pv_wanted ? op->d_pv.p : nullptr;
+  if (!a.pv) {
+    op->pv_pending = true;
+    op->pv_u       = u;
+    op->pv_stream  = joined_on ? *joined_on : st;
+  }
   a.fdiv       = op->keep_fdiv ? op->d_fdiv.p : nullptr;
   a.n_buckets  = (int32_t)op->d_blk_max.n;
   a.bucket_off = 0;
@@ -1652,9 +1666,35 @@ static int field_ptr_internal(RDyHipOperator op, RDyHipField field, double **dev
   return 0;
 }
 
+// The primitive variables leave the library: from now on every launch stores them (as every launch did before they became
+// optional), and if evaluations have run without storing, the array is brought up to date first -- all owned rows, from the
+// input state of the most recent of them, on the stream the caller ordered that evaluation on.
+static int pv_hand_out(RDyHipOperator op) {
+  op->pv_wanted = true;
+  if (!op->pv_pending) return 0;
+  op->pv_pending = false;  // whatever happens below: the next evaluation stores
+  const double *u = op->pv_u;
+  op->pv_u        = nullptr;
+  if (op->n_owned == 0) return 0;
+  // the remembered array is the caller's: launch nothing on a pointer the runtime does not know as memory of this device
+  // (an array that was freed and allocated again, or overwritten since, cannot be told: see rdyhip_field_ptr in rdyhip.h)
+  hipPointerAttribute_t at{};
+  const hipError_t      e = u ? hipPointerGetAttributes(&at, u) : hipErrorInvalidValue;
+  if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.device != op->device) {
+    (void)hipGetLastError();
+    return fail(RDYHIP_ERR_USER, "primitive variables: the state array of the last evaluation is gone (not device memory of device %d any more); "
+                                 "the next evaluation will store them", op->device);
+  }
+  hipLaunchKernelGGL(primitive_variables_kernel, dim3((unsigned)((op->n_owned + 255) / 256)), dim3(256), 0, op->pv_stream, op->n_owned,
+                     op->prefix ? nullptr : op->d_o2l.p, op->config.tiny_h, op->config.h_anuga_regular * op->config.h_anuga_regular, u, op->d_pv.p);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 int rdyhip_field_ptr(RDyHipOperator op, RDyHipField field, double **device_ptr, int64_t *num_values) {
   int rc = field_ptr_internal(op, field, device_ptr, num_values);
   if (rc) return rc;
+  if (field == RDYHIP_FIELD_PRIMITIVE_VARIABLES) return pv_hand_out(op);
   if (field == RDYHIP_FIELD_EXTERNAL_SOURCES) {
     // the caller may write the array in place at any time from now on: the water plane cannot be kept, for good
     op->src_escaped    = true;
@@ -1668,6 +1708,20 @@ int rdyhip_field_ptr_const(RDyHipOperator op, RDyHipField field, const double **
   int     rc = field_ptr_internal(op, field, device_ptr ? &p : nullptr, num_values);
   if (rc) return rc;
   *device_ptr = p;
+  if (field == RDYHIP_FIELD_PRIMITIVE_VARIABLES) return pv_hand_out(op);
+  return 0;
+}
+
+int rdyhip_field_release(RDyHipOperator op, RDyHipField field) {
+  if (field != RDYHIP_FIELD_PRIMITIVE_VARIABLES) return fail(RDYHIP_ERR_USER, "only the primitive variables can be released (field %d)", (int)field);
+  if (!op) return fail(RDYHIP_ERR_USER, "null operator");
+  op->pv_wanted = false;  // the array stays as the last storing evaluation left it until somebody asks again
+  return 0;
+}
+
+int rdyhip_primitive_variables_stored(RDyHipOperator op, int32_t *out) {
+  if (!op || !out) return fail(RDYHIP_ERR_USER, "null argument");
+  *out = op->pv_wanted ? 1 : 0;
   return 0;
 }
 

@@ -112,7 +112,7 @@ struct KernelArgs {
   const double  *dzdx, *dzdy;  // [n_owned]
   const double  *mannings;   // [n_owned]
   const double  *extsrc;     // src_mom = 1: [n_owned][3]; src_mom = 0: [n_owned], the water component alone
-  double        *pv;         // [n_owned][3]
+  double        *pv;         // [n_owned][3] or nullptr: nobody has asked for the primitive variables, they are not stored
   double        *fdiv;       // [n_owned][3] or nullptr
   double        *u_out;      // EULER kernels: [num_cells][3] state after the step, owned rows written (u_out = u + dt F)
   const ColdArgs *cold;      // device memory: see above
@@ -198,9 +198,12 @@ __device__ __forceinline__ void cell_epilogue(const KernelArgs &a, int o, double
   f[3 * (int64_t)o + 1] = acc1 + (-bedx - tbx + s1);
   f[3 * (int64_t)o + 2] = acc2 + (-bedy - tby + s2);
   // primitive variables (swe_petsc.c:788-791): the regularised velocities of the Riemann states, zero below tiny_h
-  a.pv[3 * (int64_t)o + 0] = h;
-  a.pv[3 * (int64_t)o + 1] = pu;
-  a.pv[3 * (int64_t)o + 2] = pv_;
+  // (stored once somebody has asked for them: KernelArgs::pv)
+  if (a.pv) {
+    a.pv[3 * (int64_t)o + 0] = h;
+    a.pv[3 * (int64_t)o + 1] = pu;
+    a.pv[3 * (int64_t)o + 2] = pv_;
+  }
 }
 
 // F of a cell into out[3], for the tiled kernels (they store whole rows per wave: wave_store_rows3)
@@ -893,7 +896,8 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(3, 3))) vo
         const int64_t base  = 3 * ((int64_t)o - lane);
         const int     ncell = nc_cur - (tid - lane);  // the wave's cells of this tile
         if (!EULER || f) wave_store_rows3<FNT>(f, base, lane, ncell, out[0], out[1], out[2]);
-        wave_store_rows3(a.pv, base, lane, ncell, out[3], out[4], out[5]);
+        // the primitive variables only once somebody has asked for them (KernelArgs::pv); a branch with ONE arm, like fdiv's
+        if (a.pv) wave_store_rows3(a.pv, base, lane, ncell, out[3], out[4], out[5]);
         if (a.fdiv) wave_store_rows3(a.fdiv, base, lane, ncell, acc_fdiv[0], acc_fdiv[1], acc_fdiv[2]);
         if (EULER) {
           const double n0 = out[3] + dt * out[0], n1 = own_hu + dt * out[1], n2 = own_hv + dt * out[2];
@@ -1141,6 +1145,18 @@ __global__ void euler_out_kernel(int n_owned, const int32_t *__restrict__ o2l, d
     j           = 3 * (int64_t)o2l[o] + comp;
   }
   u_out[j] = u_in[j] + dt * f[i];
+}
+// pv[owned cell o] = (h, u, v) of u[o]: the primitive variables that the RHS kernels store once somebody has asked for them
+// (KernelArgs::pv), for the first request after evaluations that did not.  The same riemann_side as theirs: the same bits.
+__global__ void primitive_variables_kernel(int n_owned, const int32_t *__restrict__ o2l, double tiny_h, double h_anuga_sq, const double *__restrict__ u,
+                                           double *__restrict__ pv) {
+  const int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (o >= n_owned) return;
+  const int64_t     c = o2l ? o2l[o] : o;
+  const RiemannSide s = riemann_side(u[3 * c + 0], u[3 * c + 1], u[3 * c + 2], tiny_h, h_anuga_sq);
+  pv[3 * o + 0]       = s.h;
+  pv[3 * o + 1]       = s.u;
+  pv[3 * o + 2]       = s.v;
 }
 __global__ void scatter_component_kernel(int n, const int32_t *__restrict__ ids, const double *__restrict__ vals, double *__restrict__ dst, int ncomp,
                                          int comp) {

@@ -463,6 +463,7 @@ class HaloExchange:
             from . import _lib
             lib = _lib.load()
             st = int(torch.cuda.current_stream(self.device).cuda_stream)
+            op._last_state = u_local   # see Operator._last_state
             if u_out is not None:
                 _lib.check(lib.rdyhip_euler_step_overlapped(op._h, self._halo, float(dt), int(u_local.data_ptr()), int(u_out.data_ptr()), None, st))
             else:

@@ -162,6 +162,11 @@ class Operator:
         except Exception:
             pass
 
+    # The state tensor of the most recent evaluation stays alive with the operator: while the primitive variables are not
+    # stored, the first request for them reads it (rdyhip_field_ptr in include/rdyhip.h) -- a caller that drops its own
+    # reference right after the call must not hand the memory back to the allocator.  In-place writes remain the caller's.
+    _last_state = None
+
     # -- argument checks shared by the apply calls -------------------------
     def _check_vecs(self, u_local: torch.Tensor, f_global: torch.Tensor):
         for name, t, n in (("u_local", u_local, self.mesh.num_cells), ("f_global", f_global, self.mesh.num_owned_cells)):
@@ -174,17 +179,20 @@ class Operator:
     # -- ApplyOperator (src/operator.c:680-690): f_global += F(u_local) ----
     def apply(self, dt: float, u_local: torch.Tensor, f_global: torch.Tensor):
         self._check_vecs(u_local, f_global)
+        self._last_state = u_local
         _lib.check(_lib.load().rdyhip_apply(self._h, float(dt), _ptr(u_local), _ptr(f_global), _stream()))
 
     # -- OperatorRHSFunction's zero + reset + apply (src/rdysetup.c:1130-1139), fused
     def rhs_function(self, dt: float, u_local: torch.Tensor, f_global: torch.Tensor):
         self._check_vecs(u_local, f_global)
+        self._last_state = u_local
         _lib.check(_lib.load().rdyhip_rhs_function(self._h, float(dt), _ptr(u_local), _ptr(f_global), _stream()))
 
     def apply_phase(self, phase: int, overwrite: bool, dt: float, u_local: torch.Tensor, f_global: torch.Tensor,
                     reset_diagnostics: bool = False, gradients_ready: bool = False):
         self._check_vecs(u_local, f_global)
         flags = (1 if overwrite else 0) | (2 if reset_diagnostics else 0) | (4 if gradients_ready else 0)
+        self._last_state = u_local
         _lib.check(_lib.load().rdyhip_apply_phase(self._h, int(phase), flags, float(dt), _ptr(u_local),
                                                  _ptr(f_global), _stream()))
 
@@ -200,6 +208,7 @@ class Operator:
         if f_global is not None:
             self._check_vecs(u_local, f_global)
         flags = (2 if reset_diagnostics else 0) | (4 if gradients_ready else 0)
+        self._last_state = u_local
         _lib.check(_lib.load().rdyhip_euler_step(self._h, int(phase), flags, float(dt), _ptr(u_local), _ptr(u_out),
                                                  _ptr(f_global) if f_global is not None else None, _stream()))
 
@@ -304,8 +313,22 @@ class Operator:
 
     @property
     def primitive_variables(self) -> torch.Tensor:
-        """Operator.primitive_variables: [owned,3] (h,u,v), written by every apply."""
+        """Operator.primitive_variables: [owned,3] (h,u,v).  Written by every evaluation from the first time it is asked for
+        (until release_primitive_variables); asked for after evaluations that did not store them, it is first filled from the
+        u_local of the most recent one, which must still hold that state (rdyhip_field_ptr in include/rdyhip.h; the operator
+        keeps that tensor alive, writing it in place before asking is the caller's business)."""
         return self._field(0, 3)
+
+    def release_primitive_variables(self):
+        """rdyhip_field_release: tensors obtained from `primitive_variables` are not read until it is asked for again;
+        evaluations stop storing them."""
+        _lib.check(_lib.load().rdyhip_field_release(self._h, 0))
+
+    def primitive_variables_stored(self) -> bool:
+        """rdyhip_primitive_variables_stored: evaluations store the primitive variables (somebody has asked for them)."""
+        out = C.c_int32()
+        _lib.check(_lib.load().rdyhip_primitive_variables_stored(self._h, C.byref(out)))
+        return bool(out.value)
 
     @property
     def external_sources(self) -> torch.Tensor:
