@@ -560,6 +560,10 @@ int rdyhip_layout_info(RDyHipOperator op, RDyHipLayoutInfo *info);
  * machine without a GPU; device_bytes and persistent_grid are 0 */
 int rdyhip_probe_layout(const RDyHipConfig *config, const RDyHipMesh *mesh, int32_t num_boundaries, const RDyHipBoundary *boundaries,
                         RDyHipLayoutInfo *info);
+/* resident workgroups per CU the first-order / HR tiled kernels of one family were built for (3 or 4; 0 for arguments that name
+ * no family): slots_per_cell 3 | 4, source_method RDYHIP_SOURCE_*, hydrostatic_reconstruction 0 | 1.  A compile-time property
+ * of the library, no device needed; persistent_grid of rdyhip_layout_info is this times the CU count unless a knob overrides it */
+int32_t rdyhip_tiled_workgroups_per_cu(int32_t slots_per_cell, int32_t source_method, int32_t hydrostatic_reconstruction);
 
 #ifdef __cplusplus
 }

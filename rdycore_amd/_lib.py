@@ -129,6 +129,7 @@ SYMBOLS = {
     "rdyhip_probe_layout": (C.c_int, [C.POINTER(RDyHipConfig), C.POINTER(RDyHipMesh), C.c_int32, C.POINTER(RDyHipBoundary),
                                       C.POINTER(RDyHipLayoutInfo)]),
     "rdyhip_layout_info": (C.c_int, [_H, C.POINTER(RDyHipLayoutInfo)]),
+    "rdyhip_tiled_workgroups_per_cu": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32]),
 }
 
 # RDyHipTransportFn: int (*)(void *ctx, const double *d_send, double *d_recv, int32_t ncomp, void *stream)

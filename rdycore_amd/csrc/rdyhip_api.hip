@@ -1076,6 +1076,8 @@ int rdyhip_create(const RDyHipConfig *config, const RDyHipMesh *mesh, int32_t nu
     int q = 0;
     const void *kfn = (const void *)tiled_kernel_fn(S, config->source_method == RDYHIP_SOURCE_IMPLICIT_XQ2018 ? 1 : 0, true, hr_on, false, true);
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, kfn, TILE, lds_bytes) == hipSuccess && q > 0) per_cu = q;
+    // the family's own setting (tiled_blocks_per_cu): a kernel compiled for three waves per SIMD may well fit four
+    per_cu = std::min(per_cu, tiled_blocks_per_cu(S, config->source_method == RDYHIP_SOURCE_IMPLICIT_XQ2018 ? 1 : 0, hr_on));
     if (const char *e2 = getenv("RDYHIP_BLOCKS_PER_CU")) {
       if (atoi(e2) > 0) per_cu = atoi(e2);
     }
@@ -1849,6 +1851,11 @@ int rdyhip_copy_owned_rows(RDyHipOperator op, const double *u_global, double *u_
   hipLaunchKernelGGL(copy_owned_rows_kernel, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, op->n_owned, op->d_o2l.p, u_global, u_local);
   HIP_TRY(hipGetLastError());
   return 0;
+}
+
+int32_t rdyhip_tiled_workgroups_per_cu(int32_t slots_per_cell, int32_t source_method, int32_t hydrostatic_reconstruction) {
+  if ((slots_per_cell != 3 && slots_per_cell != 4) || (source_method != RDYHIP_SOURCE_SEMI_IMPLICIT && source_method != RDYHIP_SOURCE_IMPLICIT_XQ2018)) return 0;
+  return tiled_blocks_per_cu(slots_per_cell, source_method == RDYHIP_SOURCE_IMPLICIT_XQ2018 ? 1 : 0, hydrostatic_reconstruction != 0);
 }
 
 int rdyhip_probe_layout(const RDyHipConfig *config, const RDyHipMesh *mesh, int32_t num_boundaries, const RDyHipBoundary *boundaries,

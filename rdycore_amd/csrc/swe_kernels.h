@@ -457,10 +457,14 @@ __device__ __forceinline__ void load_streams(const KernelArgs &a, int o, bool ac
 // Persistent, software-pipelined form: a workgroup walks a sequence of tiles.
 // All index and geometry data is static and u is read-only during the launch,
 // so every global load of tile T+1 is issued while tile T is being computed
-// (and the halo-cell ids of T+2 as well): its per-cell streams at the top of
-// T, its cell states and edge records after T's first barrier.  A tile never
-// waits for a dependent chain of global loads, and every load has about one
-// tile time to complete, which is what keeps HBM busy at 3 workgroups per CU.
+// (and the halo-cell ids of T+2 as well): its cell states and edge records
+// after T's first barrier, its per-cell streams at the end of T, into the
+// registers T's phase 2 has just read for the last time.  A tile never waits
+// for a dependent chain of global loads.  The states and records have a flux
+// phase to complete, the streams the store phase, phase 0 and the flux phase
+// of the next tile -- only phase 2 reads them, each lane its own, so ONE
+// generation of them is enough, and the registers of the second one are what
+// lets a family run four workgroups per CU (tiled_blocks_per_cu).
 //
 // HR = hydrostatic reconstruction (ApplyInteriorFluxHR, src/swe/swe_petsc.c:1000-1161):
 // each interior edge's two depths are reconstructed against max(zc_l, zc_r) before
@@ -550,9 +554,14 @@ constexpr int TILED_NS_TRI = TILE + TILE_MAX_HALO_TRI, TILED_NS_QUAD = TILE + TI
 constexpr size_t tiled_lds_bytes(int S, bool hr) {
   return sizeof(double) * ((hr ? 6 : 5) * (size_t)(S == 3 ? TILED_NS_TRI : TILED_NS_QUAD) + 2 * (size_t)TILE + (hr ? 6 : 4) * (size_t)TILED_NE);
 }
+// Workgroups per CU (= waves per SIMD: a workgroup is one wave on each of the four SIMDs) of a (S, SRC, HR) family.  The
+// persistent grid is sized once per operator and every call form runs on it, so all six OVW / EULER / FNT instantiations
+// of a family share the setting.  Four needs <= 128 VGPRs and 4 x tiled_lds_bytes <= 160 KB: the HR workgroup (46 KB) cannot,
+// the others are set by their own A/B timings (profiles/RESULTS_LOG.md section 15).
+constexpr int tiled_blocks_per_cu(int S, int SRC, bool hr) { return (S == 3 && SRC == 0 && !hr) ? 4 : 3; }
 // FNT = false: F (EULER: u_out) is stored without the non-temporal hint (RDYHIP_CONFIG_CACHED_F_STORES / states that fit the Infinity Cache)
 template <int S, int SRC, bool OVW, bool HR, bool EULER = false, bool FNT = true>
-__global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(3, 3))) void swe_rhs_tiled_kernel(const KernelArgs a, const double dt, const double *__restrict__ u,
+__global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(tiled_blocks_per_cu(S, SRC, HR), tiled_blocks_per_cu(S, SRC, HR)))) void swe_rhs_tiled_kernel(const KernelArgs a, const double dt, const double *__restrict__ u,
                                                               double *__restrict__ f) {
   // edge-record rounds held in registers: every tile has <= TILE_MAX_REC = 2 x 256 edge records (a 256-cell tile of a
   // well-numbered triangle mesh 1.6 per cell; a quad tile is cut at 240 cells, a 16 x 15 block = 511 records; round 4 ran
@@ -642,6 +651,11 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(3, 3))) vo
       const int o1 = td1.c_off + tid;
       c1           = (a.o2l && tid < td1.nc()) ? a.o2l[o1] : o1;
     }
+    // The prologue's state, records and ids are waited for HERE, once per workgroup.  Left to the first use inside the loop
+    // (phase 0), the wait would stand at the top of every tile -- hipcc orders the prologue's loads as it likes, so it is a
+    // vmcnt(0) -- and drain the streams issued at the end of the previous tile before they had any time at all.
+    asm volatile("" ::"v"(pu0), "v"(pu1), "v"(pu2), "v"(ph0), "v"(ph1), "v"(ph2), "v"(pz), "v"(phz), "v"(lr0), "v"(lr1), "v"(cs0), "v"(cs1), "v"(hid1),
+                 "v"(c1));
 
     while (true) {
       const int  ne = td.ne(), nh = td.nh();
@@ -667,12 +681,14 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(3, 3))) vo
       }
       __syncthreads();
 
-      // ---- software pipeline: EVERY global load of the next tile (cell states, edge records, per-cell
-      // streams) and the halo ids of the one after are issued here in one batch.  hipcc waits with
-      // s_waitcnt vmcnt(0) wherever a loaded register is first used, so the batch must not be followed
-      // by any such use until the end of the tile: phases 1 and 2 below touch only registers whose
-      // loads completed a tile ago, and the first use of this batch is the register rotation at the
-      // very end (one wait per tile, a whole flux phase after the loads were issued).
+      // ---- software pipeline: the cell states and edge records of the next tile and the halo ids of the
+      // one after are issued here in one batch (its per-cell streams follow at the end of this tile).
+      // hipcc waits with s_waitcnt vmcnt(0) wherever a loaded register is first used, so nothing this
+      // batch loads is used until the register rotation at the very end.  Two waits per tile on the hot
+      // path: the one on this tile's streams after the second barrier -- a whole flux phase after this
+      // batch was issued; it is a vmcnt(0) too, every load of the batch sits under a predicate and hipcc
+      // can count none of them as issued (the branch-free form that lets it wait with vmcnt(8) was
+      // timed: 1.3 % slower, profiles/RESULTS_LOG.md section 15) -- and the one at the end of the tile.
       // (a) which tile comes after the next, and the ids it needs (the only dependent loads: first)
       __builtin_amdgcn_s_setprio(3);  // waves that reach their load batch issue it ahead of waves that are computing (+0.7..1 %)
       int      idx2 = hi, tile2 = 0, hid2 = 0, c2 = 0;
@@ -691,7 +707,6 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(3, 3))) vo
       uint32_t nlr0 = 0, nlr1 = 0;
       double   ncs0 = 0.0, ncs1 = 0.0;
       int      npos_lo = 0, npos_q = 0;
-      CellStreams<S> nxt;
       if (idx1 < hi) {
         npos_lo = load_uniform(RDY_COLD(a, e_pos), td1.e_off);
         npos_q  = load_uniform(RDY_COLD(a, e_pos), td1.e_off + min(COURANT_Q, td1.ne() - 1));
@@ -707,7 +722,6 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(3, 3))) vo
         if (tid < ne1) { nlr0 = RDY_LD(&a.e_lr[td1.e_off + tid]); ncs0 = RDY_LD(&a.e_cs[td1.e_off + tid]); }
         if (tid + TILE < ne1) { nlr1 = RDY_LD(&a.e_lr[td1.e_off + TILE + tid]); ncs1 = RDY_LD(&a.e_cs[td1.e_off + TILE + tid]); }
       }
-      load_streams<S, HR>(a, td1.c_off + tid, idx1 < hi && tid < td1.nc(), nxt);
       __builtin_amdgcn_s_setprio(0);
 
       // ---- phase 1: every edge of the tile once, operands from LDS only
@@ -783,6 +797,10 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(3, 3))) vo
         if (e < ne) do_edge(e, r == 0 ? lr0 : lr1, r == 0 ? cs0 : cs1);
       }
       __syncthreads();
+      // The tile's wait on its per-cell streams, once, ahead of every use: they were issued at the end of the previous tile
+      // (the first tile's in the prologue), before that tile's stores and this tile's batch.
+      asm volatile("" ::"v"(cur.r0), "v"(cur.r1), "v"(cur.coef[0]), "v"(cur.coef[1]), "v"(cur.coef[2]), "v"(cur.coef[S - 1]), "v"(cur.dzdx),
+                   "v"(cur.dzdy), "v"(cur.nman), "v"(cur.s0), "v"(cur.s1), "v"(cur.s2));
 
       // ---- phase 2: per-cell sum in the reference's edge order, source terms; the stores come last
       double out[6]      = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // F[3], then the primitive variables (h, u, v)
@@ -870,13 +888,11 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(3, 3))) vo
         }
       }
       const bool last = idx1 >= hi;
-      // The tile's single wait on global loads: the youngest load of the prefetch batch is "used" here, before
-      // this tile's stores are issued (vmcnt counts stores too, and the register rotation below is
-      // materialised at the very end of the loop body).
+      // The tile's wait on the prefetch batch: its youngest load is "used" here, before this tile's stores are
+      // issued (vmcnt counts stores too, and the register rotation below is materialised at the very end of the
+      // loop body).
       asm volatile("" ::"v"(pu0), "v"(pu1), "v"(pu2), "v"(ph0), "v"(ph1), "v"(ph2), "v"(pz), "v"(phz), "v"(nlr0), "v"(nlr1), "v"(ncs0), "v"(ncs1),
                    "v"(hid2), "v"(c2));
-      asm volatile("" ::"v"(nxt.r0), "v"(nxt.r1), "v"(nxt.coef[0]), "v"(nxt.coef[1]), "v"(nxt.coef[2]), "v"(nxt.coef[S - 1]), "v"(nxt.dzdx),
-                   "v"(nxt.dzdy), "v"(nxt.nman), "v"(nxt.s0), "v"(nxt.s1), "v"(nxt.s2));
       // rotate the pipeline registers, store
       const bool send_tile = EULER && td.send();  // wave-uniform
       const int  tile_cur  = tile, nc_cur = td.nc();
@@ -885,7 +901,9 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(3, 3))) vo
       pos_lo = npos_lo;
       pos_q  = npos_q;
       lr0 = nlr0; lr1 = nlr1; cs0 = ncs0; cs1 = ncs1;
-      cur = nxt;
+      // the next tile's per-cell streams, into the registers phase 2 (its cold Courant tie path included) has just read
+      // for the last time; not on the workgroup's last tile
+      load_streams<S, HR>(a, td.c_off + tid, !last && tid < td.nc(), cur);
       __builtin_amdgcn_sched_barrier(0);
       // F, pv (and fdiv, u_out) are [cell][3]: a wave's 64 cells own 192 consecutive doubles of each.  The rows are
       // transposed through wave shuffles so that every store instruction writes 512 contiguous bytes (whole lines)
