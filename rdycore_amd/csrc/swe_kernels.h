@@ -148,6 +148,26 @@ __device__ __forceinline__ T load_uniform(const T *p, int i) {
 // a field of the device-resident ColdArgs block: one scalar load at the point of use
 #define RDY_COLD(a, field) (load_uniform(&(a).cold->field, 0))
 
+// The explicit arguments of the tiled kernel as they lie in its kernarg segment.  Pointers that the tile loop uses once per tile
+// (the per-cell stream arrays, the output arrays, u) are fetched from there with scalar loads where they are used (RDY_HOT), a
+// whole group per s_load, instead of being kept in SGPRs across the loop: held for the launch they do not fit beside the three
+// tile descriptors and the loop state, hipcc spills them to VGPR lanes and restores them -- sixteen at a time, one VALU
+// instruction per register -- in the middle of the blocks that issue the loads (profiles/RESULTS_LOG.md section 16).  The
+// segment's address goes through an empty asm once per use site: a new value per tile as far as the optimiser knows, so the
+// loads stay where they are written instead of being hoisted out of the loop and spilled again.
+struct TiledKernargs {
+  KernelArgs    a;
+  double        dt;
+  const double *u;
+  double       *f;
+};
+typedef const __attribute__((address_space(4))) TiledKernargs *HotArgs;
+__device__ __forceinline__ HotArgs hot_kernargs() {
+  uint64_t p = (uint64_t)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return (HotArgs)p;
+}
+
 // The workgroup's block of cells in the cell-centric kernels.  Block ids are dealt round-robin to the 8 XCDs: with
 // xcd_chunks > 0 (KernelArgs) each XCD gets a contiguous range of blocks, so concurrently running blocks are neighbours.
 // (Takes the count, not the KernelArgs: read through a reference here, it moves the kernels' code.)
@@ -234,6 +254,53 @@ __device__ __forceinline__ void wave_store_rows3(double *__restrict__ arr, int64
       if (NT) RDY_ST(&arr[base + e], comp == 0 ? s0 : (comp == 1 ? s1 : s2));
       else arr[base + e] = comp == 0 ? s0 : (comp == 1 ? s1 : s2);
     }
+  }
+}
+
+// The same stores with the transpose done through 192 doubles of LDS that belong to the wave alone at that point, instead of
+// nine 64-bit shuffles (18 ds_bpermute_b32) and a three-way select per stored value: lane l writes its row to elements
+// 3 l .. 3 l + 2, then reads elements l, 64 + l, 128 + l.  `wr`: the lane's three write slots, `rd`: element `lane`; the
+// elements are 64-entry pieces of three planes a fixed distance `plane` apart (the tiled kernel passes its own cells' entries
+// of sd_v, sd_sq and sd_c: phase 1 was their last reader, before the second barrier; the wave itself rewrites them in phase 0
+// of its next tile).  LDS serves a wave's instructions in order, so a read returns what the write before it stored; the
+// wave-scope fences only keep the compiler from reordering the two across lanes' addresses it cannot tell apart.
+struct RowTranspose {
+  double *wr[3];
+  double *rd;
+};
+template <int PLANE>
+__device__ __forceinline__ RowTranspose row_transpose_slots(double *wave_plane0, int lane) {
+  RowTranspose t;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const int e = 3 * lane + j;
+    t.wr[j]     = wave_plane0 + (e >> 6) * PLANE + (e & 63);
+  }
+  t.rd = wave_plane0 + lane;
+  return t;
+}
+template <int PLANE, bool NT = true>
+__device__ __forceinline__ void wave_store_rows3_lds(double *__restrict__ arr, int64_t base, int lane, int ncell, const RowTranspose &t, double v0, double v1,
+                                                     double v2) {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // the reads of the array before this one come first
+  __builtin_amdgcn_wave_barrier();
+  *t.wr[0] = v0;
+  *t.wr[1] = v1;
+  *t.wr[2] = v2;
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  const double s0 = t.rd[0], s1 = t.rd[PLANE], s2 = t.rd[2 * PLANE];
+  double *row = arr + (base + lane);
+  // element 64 k + lane belongs to cell (64 k + lane) / 3 of the wave: stored if that cell exists, i.e. 64 k + lane < 3 ncell
+  const int e = 3 * ncell - lane;
+  if (NT) {
+    if (e > 0) RDY_ST(&row[0], s0);
+    if (e > 64) RDY_ST(&row[64], s1);
+    if (e > 128) RDY_ST(&row[128], s2);
+  } else {
+    if (e > 0) row[0] = s0;
+    if (e > 64) row[64] = s1;
+    if (e > 128) row[128] = s2;
   }
 }
 
@@ -423,12 +490,31 @@ struct CellStreams {
   double   dzdx, dzdy, nman, s0, s1, s2;
 };
 
+// The pointers and the two scalars load_streams reads: filled from the kernarg segment where the streams are issued (RDY_HOT)
+struct StreamArgs {
+  const void   *slot_ref;
+  const double *coef, *dzdx, *dzdy, *mannings, *extsrc;
+  int64_t       stride;
+  int32_t       src_mom;
+};
+__device__ __forceinline__ StreamArgs stream_args(HotArgs k) {
+  StreamArgs p;
+  p.slot_ref = k->a.slot_ref;
+  p.coef     = k->a.coef;
+  p.dzdx     = k->a.dzdx;
+  p.dzdy     = k->a.dzdy;
+  p.mannings = k->a.mannings;
+  p.extsrc   = k->a.extsrc;
+  p.stride   = k->a.stride;
+  p.src_mom  = k->a.src_mom;
+  return p;
+}
+
+// Only the lanes that hold a cell load, and only they read `c` afterwards: phase 2 runs under the same count (tid < td.nc())
+// and the arrival points name registers, not values.  The other lanes' registers are left as they are -- setting them cost
+// ten moves per tile.
 template <int S, bool HR>
-__device__ __forceinline__ void load_streams(const KernelArgs &a, int o, bool active, CellStreams<S> &c) {
-  c.r0 = c.r1 = 0xFFFFFFFFu;
-#pragma unroll
-  for (int s = 0; s < S; ++s) c.coef[s] = 0.0;
-  c.dzdx = c.dzdy = c.nman = c.s0 = c.s1 = c.s2 = 0.0;
+__device__ __forceinline__ void load_streams(const StreamArgs &a, int o, bool active, CellStreams<S> &c) {
   if (active) {
     if (S == 3) {
       c.r0 = RDY_LD(&reinterpret_cast<const uint32_t *>(a.slot_ref)[o]);
@@ -442,12 +528,15 @@ __device__ __forceinline__ void load_streams(const KernelArgs &a, int o, bool ac
     if (!HR) {  // under HR the pressure correction of the flux carries the bed slope
       c.dzdx = RDY_LD(&a.dzdx[o]);
       c.dzdy = RDY_LD(&a.dzdy[o]);
+    } else {
+      c.dzdx = c.dzdy = 0.0;
     }
     c.nman = RDY_LD(&a.mannings[o]);
     // the water source: row o of the [owned][3] array, or entry o of the water plane, which costs 8 B of HBM traffic per cell
     // instead of the 24 B that any read of a 24-B row does
     c.s0 = RDY_LD(&a.extsrc[a.src_mom ? 3 * (int64_t)o : (int64_t)o]);
-    if (a.src_mom) {  // wave-uniform; otherwise the momentum sources stay the zeros set above
+    c.s1 = c.s2 = 0.0;
+    if (a.src_mom) {  // wave-uniform; otherwise the momentum sources are the zeros just set
       c.s1 = RDY_LD(&a.extsrc[3 * (int64_t)o + 1]);
       c.s2 = RDY_LD(&a.extsrc[3 * (int64_t)o + 2]);
     }
@@ -619,7 +708,9 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(tiled_bloc
     double   pz = 0.0, phz = 0.0;              // HR: bed elevation of the own / halo cell
     uint32_t lr0 = 0, lr1 = 0;                 // the two rounds of edge records
     double   cs0 = 0.0, cs1 = 0.0;
-    CellStreams<S> cur;
+    CellStreams<S> cur{};  // set once: a lane without a cell keeps what it has, nobody reads it (load_streams)
+    uint32_t nlr0 = 0, nlr1 = 0;  // the next tile's records, loaded under the counts phase 1 tests: no per-tile reset either
+    double   ncs0 = 0.0, ncs1 = 0.0;
     {
       const int o = td.c_off + tid;
       if (tid < td.nc()) {
@@ -635,7 +726,7 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(tiled_bloc
       const int ne = td.ne();
       if (tid < ne) { lr0 = RDY_LD(&a.e_lr[td.e_off + tid]); cs0 = RDY_LD(&a.e_cs[td.e_off + tid]); }
       if (tid + TILE < ne) { lr1 = RDY_LD(&a.e_lr[td.e_off + TILE + tid]); cs1 = RDY_LD(&a.e_cs[td.e_off + TILE + tid]); }
-      load_streams<S, HR>(a, o, tid < td.nc(), cur);
+      load_streams<S, HR>(stream_args(hot_kernargs()), o, tid < td.nc(), cur);
     }
     // the loop positions of the tile's records 0 and COURANT_Q (sorted by position): what lets the Courant tie path dismiss a
     // candidate without touching memory (CourantTrack); fetched a tile ahead like everything else
@@ -704,18 +795,17 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(tiled_bloc
         }
       }
       // (b) the next tile's cell states, edge records and per-cell streams
-      uint32_t nlr0 = 0, nlr1 = 0;
-      double   ncs0 = 0.0, ncs1 = 0.0;
       int      npos_lo = 0, npos_q = 0;
       if (idx1 < hi) {
+        const double *const ub = hot_kernargs()->u;  // fetched beside the tile descriptor, not held across the loop
         npos_lo = load_uniform(RDY_COLD(a, e_pos), td1.e_off);
         npos_q  = load_uniform(RDY_COLD(a, e_pos), td1.e_off + min(COURANT_Q, td1.ne() - 1));
         if (tid < td1.nc()) {
-          pu0 = u[3 * (int64_t)c1 + 0]; pu1 = u[3 * (int64_t)c1 + 1]; pu2 = u[3 * (int64_t)c1 + 2];
+          pu0 = ub[3 * (int64_t)c1 + 0]; pu1 = ub[3 * (int64_t)c1 + 1]; pu2 = ub[3 * (int64_t)c1 + 2];
           if (HR) pz = a.zc_local[c1];
         }
         if (tid < td1.nh()) {
-          ph0 = u[3 * (int64_t)hid1 + 0]; ph1 = u[3 * (int64_t)hid1 + 1]; ph2 = u[3 * (int64_t)hid1 + 2];
+          ph0 = ub[3 * (int64_t)hid1 + 0]; ph1 = ub[3 * (int64_t)hid1 + 1]; ph2 = ub[3 * (int64_t)hid1 + 2];
           if (HR) phz = a.zc_local[hid1];
         }
         const int ne1 = td1.ne();
@@ -801,6 +891,11 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(tiled_bloc
       // (the first tile's in the prologue), before that tile's stores and this tile's batch.
       asm volatile("" ::"v"(cur.r0), "v"(cur.r1), "v"(cur.coef[0]), "v"(cur.coef[1]), "v"(cur.coef[2]), "v"(cur.coef[S - 1]), "v"(cur.dzdx),
                    "v"(cur.dzdy), "v"(cur.nman), "v"(cur.s0), "v"(cur.s1), "v"(cur.s2));
+      // what the end of the tile reads once -- the stream arrays of the next tile's loads, the output arrays -- comes from the
+      // kernarg segment here, a whole phase 2 ahead of its use
+      const HotArgs    hk = hot_kernargs();
+      const StreamArgs sa = stream_args(hk);
+      double *const    f_hot = hk->f, *const pv_hot = hk->a.pv, *const fdiv_hot = hk->a.fdiv, *const uout_hot = hk->a.u_out;
 
       // ---- phase 2: per-cell sum in the reference's edge order, source terms; the stores come last
       double out[6]      = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // F[3], then the primitive variables (h, u, v)
@@ -903,7 +998,7 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(tiled_bloc
       lr0 = nlr0; lr1 = nlr1; cs0 = ncs0; cs1 = ncs1;
       // the next tile's per-cell streams, into the registers phase 2 (its cold Courant tie path included) has just read
       // for the last time; not on the workgroup's last tile
-      load_streams<S, HR>(a, td.c_off + tid, !last && tid < td.nc(), cur);
+      load_streams<S, HR>(sa, td.c_off + tid, !last && tid < td.nc(), cur);
       __builtin_amdgcn_sched_barrier(0);
       // F, pv (and fdiv, u_out) are [cell][3]: a wave's 64 cells own 192 consecutive doubles of each.  The rows are
       // transposed through wave shuffles so that every store instruction writes 512 contiguous bytes (whole lines)
@@ -913,27 +1008,30 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(tiled_bloc
         const int     lane  = tid & 63;
         const int64_t base  = 3 * ((int64_t)o - lane);
         const int     ncell = nc_cur - (tid - lane);  // the wave's cells of this tile
-        if (!EULER || f) wave_store_rows3<FNT>(f, base, lane, ncell, out[0], out[1], out[2]);
+        // the transpose goes through the wave's own 64 entries of sd_v, sd_sq and sd_c (wave_store_rows3_lds): phase 1 read
+        // them for the last time before the second barrier, out[5] has this lane's sd_v, phase 0 of the next tile rewrites them
+        const RowTranspose rt = row_transpose_slots<nside>(sd_v + (tid - lane), lane);
+        if (!EULER || f_hot) wave_store_rows3_lds<nside, FNT>(f_hot, base, lane, ncell, rt, out[0], out[1], out[2]);
         // the primitive variables only once somebody has asked for them (KernelArgs::pv); a branch with ONE arm, like fdiv's
-        if (a.pv) wave_store_rows3(a.pv, base, lane, ncell, out[3], out[4], out[5]);
-        if (a.fdiv) wave_store_rows3(a.fdiv, base, lane, ncell, acc_fdiv[0], acc_fdiv[1], acc_fdiv[2]);
+        if (pv_hot) wave_store_rows3_lds<nside>(pv_hot, base, lane, ncell, rt, out[3], out[4], out[5]);
+        if (fdiv_hot) wave_store_rows3_lds<nside>(fdiv_hot, base, lane, ncell, rt, acc_fdiv[0], acc_fdiv[1], acc_fdiv[2]);
         if (EULER) {
           const double n0 = out[3] + dt * out[0], n1 = own_hu + dt * out[1], n2 = own_hv + dt * out[2];
           if (!a.o2l) {
             // u_out is what the NEXT step reads.  With the hint it is not in the Infinity Cache then; without it, it is -- if it
             // fits: a 2.8 M-cell part (67 MB of state) steps 8 % faster with plain stores, a 10 M-cell one (240 MB of a 256 MB
             // cache) 3.5 % slower (profiles/r04_uout_store_policy.txt).  FNT = false is the instantiation for states that fit.
-            wave_store_rows3<FNT>(a.u_out, base, lane, ncell, n0, n1, n2);
+            wave_store_rows3_lds<nside, FNT>(uout_hot, base, lane, ncell, rt, n0, n1, n2);
           } else if (active) {  // owned cells are not a prefix of the local numbering: scattered rows
             const int64_t c = a.o2l[o];
             if constexpr (FNT) {
-              RDY_ST(&a.u_out[3 * c + 0], n0);
-              RDY_ST(&a.u_out[3 * c + 1], n1);
-              RDY_ST(&a.u_out[3 * c + 2], n2);
+              RDY_ST(&uout_hot[3 * c + 0], n0);
+              RDY_ST(&uout_hot[3 * c + 1], n1);
+              RDY_ST(&uout_hot[3 * c + 2], n2);
             } else {
-              a.u_out[3 * c + 0] = n0;
-              a.u_out[3 * c + 1] = n1;
-              a.u_out[3 * c + 2] = n2;
+              uout_hot[3 * c + 0] = n0;
+              uout_hot[3 * c + 1] = n1;
+              uout_hot[3 * c + 2] = n2;
             }
           }
           if (send_tile) wave_store_send_rows(a, tile_cur, tid, n0, n1, n2);
