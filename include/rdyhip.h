@@ -528,6 +528,31 @@ int rdyhip_axpy_owned(RDyHipOperator op, double dt, const double *f_global, doub
 int rdyhip_euler_step(RDyHipOperator op, int32_t phase, int32_t flags, double dt, const double *u_local, double *u_local_out, double *f_global,
                       void *stream);
 
+/* One classical Runge-Kutta step behind one call: TSStep_RK with the TSRK4 tableau (the reference's `numerics.temporal:
+ * rk4`, src/rdysetup.c:1187-1189; A = [[0], [1/2], [0, 1/2], [0, 0, 1]], b = [1/6, 1/3, 1/3, 1/6]).  u_local[owned cell]
+ * advances by dt; the four stage vectors and the stage state stay on the device, in a workspace the operator owns.
+ *   - Four stage evaluations, each what rdyhip_rhs_function does (halo NULL, or a halo without peers) or, with a halo,
+ *     what rdyhip_rhs_overlapped does: its ghost update, the form the halo has chosen for RHS-kind steps (a stage counts as
+ *     one such step in the halo's trial), the diagnostics reset.  Stage 1 runs on u_local itself (its ghost rows are
+ *     updated as by any rdyhip_rhs_overlapped); every stage gets the FULL step's dt in the friction term (TSGetTimeStep,
+ *     src/rdysetup.c:1129).  What is left behind -- Courant struct, boundary fluxes, primitive variables -- is stage 4's.
+ *   - Between them one launch per stage state (y = u + c k on the owned rows: c = dt/2, dt/2, dt) and one at the end
+ *     (u += dt/6 k1 + dt/3 k2 + dt/3 k3 + dt/6 k4, as a chain of fused multiply-adds in that order): the bits of
+ *     rdyhip_axpy_owned applied stage by stage, in 8 launches and 360 B per cell instead of 14 and 648.
+ *   - Ghost rows of the stage state that no exchange writes (halo NULL, or receive lists that leave some out) hold
+ *     u_local's values.
+ *   - Workspace: [num_cells][3] + 4 x [num_owned_cells][3] doubles, allocated by the FIRST call -- that one call may
+ *     synchronise the device; no later one does -- counted in RDyHipLayoutInfo.device_bytes from then on and freed by
+ *     rdyhip_destroy.
+ *   - The owned rows of u_local are rewritten: a fused pack (rdyhip_halo_fuse_pack) of `halo`, or of whichever halo of this
+ *     operator holds it, is invalidated as by rdyhip_halo_invalidate, so a later rdyhip_euler_step_overlapped on the same
+ *     array packs again.
+ *   - "The u_local of the most recent evaluation" (rdyhip_field_ptr, primitive variables on demand) is the operator's own
+ *     stage state after this call: it outlives the call, a first request is filled from stage 4's state.
+ * RDYHIP_ERR_USER before any device call: null op, null u_local on a rank with cells (owned or ghost), a halo of another operator.  A rank that
+ * owns nothing still takes part in the four exchanges. */
+int rdyhip_rk4_step(RDyHipOperator op, RDyHipHalo halo /* may be NULL */, double dt, double *u_local, void *stream);
+
 /* ---- introspection ----------------------------------------------------------
  * numbers describing the device layout, for DESIGN.md / bench.py */
 typedef struct {

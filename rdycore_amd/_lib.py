@@ -99,6 +99,7 @@ SYMBOLS = {
     "rdyhip_unpack_rows": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "rdyhip_axpy_owned": (C.c_int, [_H, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rdyhip_euler_step": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rdyhip_rk4_step": (C.c_int, [_H, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
     "rdyhip_halo_create": (C.c_int, [_H, C.c_void_p, C.c_int32, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p, C.POINTER(C.c_void_p)]),
     "rdyhip_halo_destroy": (C.c_int, [C.POINTER(C.c_void_p)]),
     "rdyhip_halo_overlaps": (C.c_int32, [C.c_void_p]),

@@ -22,6 +22,7 @@ struct RDyHipHalo_s {
   // every ghost this rank receives is one of a run of consecutive local rows, in arrival order (peer by peer, the agreed
   // order inside a peer: rdyhip_local_cell_order): the transfer lands in the caller's array itself, no unpack launch
   int32_t         recv_base = -1;  // first row of that run, or -1: receive into d_recv and unpack
+  bool            recv_covers_ghosts = false;  // every row of the local vector that is not an owned cell's is received (rdyhip_rk4_step)
   // rdyhip_halo_fuse_pack: the Euler-step kernels store the rows of their send-flagged cells into d_send as they store
   // u_out (per-tile send lists, swe_kernels.h), so the next step's exchange needs no pack launch either
   bool            fused_pack = false;
@@ -380,6 +381,20 @@ int rdyhip_halo_create(RDyHipOperator op, void *nccl_comm, int32_t npeers, const
       }
   }
   h->max_comp = op->muscl ? 6 : 3;
+  {
+    // does an exchange write every ghost row?  (rdyhip_rk4_step then leaves the ghost rows of its stage state to it)
+    std::vector<char> got((size_t)op->n_cells, 0);
+    int32_t           nghost = 0;
+    for (int32_t i = 0; i < nr; ++i) {
+      const int32_t c     = recv_cell_ids[i];
+      const bool    owned = op->prefix ? c < op->n_owned : (c < (int32_t)op->h_l2o.size() && op->h_l2o[(size_t)c] >= 0 && op->h_l2o[(size_t)c] < op->n_owned);
+      if (!owned && !got[(size_t)c]) {
+        got[(size_t)c] = 1;
+        ++nghost;
+      }
+    }
+    h->recv_covers_ghosts = nghost == op->n_cells - op->n_owned;
+  }
   {
     // ghosts numbered peer by peer in arrival order (rdyhip_local_cell_order): receive in place.  RDYHIP_DIRECT_RECV=0: measurement knob
     bool run = nr > 0;

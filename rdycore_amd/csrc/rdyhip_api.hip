@@ -38,6 +38,7 @@
 #include "swe_kernels.h"
 #include "forcing_kernels.h"
 #include "muscl_kernels.h"
+#include "rk_kernels.h"
 
 using namespace rdyhip;
 
@@ -195,6 +196,9 @@ struct RDyHipOperator_s {
   DevBuf<double>  d_scratch_f;   // F of rdyhip_euler_step when the caller wants none and the kernel cannot skip it
   DevBuf<double>  d_stage_vals;
   DevBuf<int32_t> d_stage_ids;
+  // rdyhip_rk4_step: the stage state [n_cells][3] and k1..k4 [n_owned][3], allocated by the first call, kept until destroy
+  DevBuf<double>  d_rk_y, d_rk_k[4];
+  bool            rk_ready = false;
 
   int64_t device_bytes = 0;
 
@@ -209,6 +213,8 @@ struct RDyHipOperator_s {
     d_e_cs.release(); d_slot_ref.release(); d_slot_ref3.release(); d_zc_local.release();
     d_grad.release(); d_e_mid.release(); d_cxy.release(); d_hcells2.release(); d_c_off.release();
     d_bn_idx.release();
+    d_rk_y.release();
+    for (auto &k : d_rk_k) k.release();
     stage.release();
   }
 };
@@ -1918,3 +1924,97 @@ int rdyhip_layout_info(RDyHipOperator op, RDyHipLayoutInfo *info) {
 
 #include "halo_exchange.h"
 #include "halo_plan.h"
+
+// ---- classical Runge-Kutta step (rk_kernels.h) ------------------------------------------------------------------------------
+namespace {
+
+// the workspace of rdyhip_rk4_step, on its first call (hipMalloc: this one call may synchronise the device)
+int rk4_workspace(RDyHipOperator op) {
+  if (op->rk_ready) return 0;
+  int rc = op->d_rk_y.alloc((size_t)3 * op->n_cells);
+  for (auto &k : op->d_rk_k)
+    if (!rc) rc = k.alloc((size_t)3 * op->n_owned);
+  if (rc) {
+    op->d_rk_y.release();
+    for (auto &k : op->d_rk_k) k.release();
+    return rc;
+  }
+  op->device_bytes += op->d_rk_y.bytes();
+  for (auto &k : op->d_rk_k) op->device_bytes += k.bytes();
+  op->rk_ready = true;
+  return 0;
+}
+
+bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+// y = u0 + c k on the owned rows; with `ghost_rows`, y's other rows = u0's
+int launch_rk4_stage(RDyHipOperator op, double c, const double *k, const double *u0, double *y, bool ghost_rows, hipStream_t st) {
+  const int64_t n_own = 3 * (int64_t)op->n_owned, n_cells3 = 3 * (int64_t)op->n_cells;
+  if (!op->prefix) {
+    if (ghost_rows && n_cells3 > 0) HIP_TRY(hipMemcpyAsync(y, u0, sizeof(double) * (size_t)n_cells3, hipMemcpyDeviceToDevice, st));
+    if (n_own == 0) return 0;
+    hipLaunchKernelGGL((rk4_stage_kernel<false>), dim3((unsigned)((n_own + RK_BLOCK - 1) / RK_BLOCK)), dim3(RK_BLOCK), 0, st, n_own, n_own,
+                       op->d_o2l.p, c, k, u0, y);
+  } else {
+    const int64_t n_all = ghost_rows ? n_cells3 : n_own;
+    if (n_all == 0) return 0;
+    if (aligned16(k) && aligned16(u0) && aligned16(y)) {
+      const int64_t pairs = (n_all + 1) / 2;
+      hipLaunchKernelGGL((rk4_stage_kernel<true>), dim3((unsigned)((pairs + RK_BLOCK - 1) / RK_BLOCK)), dim3(RK_BLOCK), 0, st, n_own, n_all,
+                         (const int32_t *)nullptr, c, k, u0, y);
+    } else {
+      hipLaunchKernelGGL((rk4_stage_kernel<false>), dim3((unsigned)((n_all + RK_BLOCK - 1) / RK_BLOCK)), dim3(RK_BLOCK), 0, st, n_own, n_all,
+                         (const int32_t *)nullptr, c, k, u0, y);
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+int launch_rk4_combine(RDyHipOperator op, double dt, double *u, hipStream_t st) {
+  const int64_t n_own = 3 * (int64_t)op->n_owned;
+  if (n_own == 0) return 0;
+  const double  c1 = (1.0 / 6.0) * dt, c2 = (1.0 / 3.0) * dt, c3 = (1.0 / 3.0) * dt, c4 = (1.0 / 6.0) * dt;
+  const double *k1 = op->d_rk_k[0].p, *k2 = op->d_rk_k[1].p, *k3 = op->d_rk_k[2].p, *k4 = op->d_rk_k[3].p;
+  if (op->prefix && aligned16(u) && aligned16(k1) && aligned16(k2) && aligned16(k3) && aligned16(k4)) {
+    const int64_t pairs = (n_own + 1) / 2;
+    hipLaunchKernelGGL((rk4_combine_kernel<true>), dim3((unsigned)((pairs + RK_BLOCK - 1) / RK_BLOCK)), dim3(RK_BLOCK), 0, st, n_own,
+                       (const int32_t *)nullptr, c1, c2, c3, c4, k1, k2, k3, k4, u);
+  } else {
+    hipLaunchKernelGGL((rk4_combine_kernel<false>), dim3((unsigned)((n_own + RK_BLOCK - 1) / RK_BLOCK)), dim3(RK_BLOCK), 0, st, n_own,
+                       op->prefix ? (const int32_t *)nullptr : op->d_o2l.p, c1, c2, c3, c4, k1, k2, k3, k4, u);
+  }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int rdyhip_rk4_step(RDyHipOperator op, RDyHipHalo halo, double dt, double *u_local, void *stream) {
+  if (!op) return fail(RDYHIP_ERR_USER, "null operator");
+  if (op->n_cells > 0 && !u_local) return fail(RDYHIP_ERR_USER, "null u_local");   // (ghost rows alone are still copied and exchanged)
+  if (halo && halo->op != op) return fail(RDYHIP_ERR_USER, "the halo belongs to another operator");
+  hipStream_t st = (hipStream_t)stream;
+  // the combine kernel writes the owned rows of u_local: a send buffer that mirrors them (rdyhip_halo_fuse_pack) is stale
+  if (halo) halo_forget_packed_state(halo);
+  if (op->fused_halo && op->fused_halo != halo) halo_forget_packed_state(op->fused_halo);
+  int rc = rk4_workspace(op);
+  if (rc) return rc;
+  const bool exchange = halo && !halo->peers.empty();
+  // every stage is OperatorRHSFunction with its ghost update and the FULL step's dt (TSGetTimeStep, src/rdysetup.c:1129)
+  auto stage_rhs = [&](double *u, double *k) -> int {
+    return exchange ? overlapped(op, halo, dt, u, k, nullptr, st) : rdyhip_rhs_function(op, dt, u, k, stream);
+  };
+  // the stage state's ghost rows: the stage's own exchange writes them where the halo receives every one of them; the
+  // others keep u_local's values
+  const bool ghost_rows = op->n_cells > op->n_owned && !(exchange && halo->recv_covers_ghosts);
+  double    *y = op->d_rk_y.p;
+  rc = stage_rhs(u_local, op->d_rk_k[0].p);
+  const double a[3] = {0.5, 0.5, 1.0};
+  for (int j = 1; j < 4 && !rc; ++j) {
+    rc = launch_rk4_stage(op, a[j - 1] * dt, op->d_rk_k[j - 1].p, u_local, y, ghost_rows, st);
+    if (!rc) rc = stage_rhs(y, op->d_rk_k[j].p);
+  }
+  if (!rc) rc = launch_rk4_combine(op, dt, u_local, st);
+  return rc;
+}

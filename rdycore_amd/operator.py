@@ -212,6 +212,21 @@ class Operator:
         _lib.check(_lib.load().rdyhip_euler_step(self._h, int(phase), flags, float(dt), _ptr(u_local), _ptr(u_out),
                                                  _ptr(f_global) if f_global is not None else None, _stream()))
 
+    # -- TSStep_RK with the TSRK4 tableau (src/rdysetup.c:1187-1189): four stage evaluations, the stage vectors on the device --
+    def rk4_step(self, dt: float, u_local: torch.Tensor, halo=None):
+        """One classical Runge-Kutta step of u_local's owned rows, in place (rdyhip_rk4_step).  `halo`: the HaloExchange of
+        a multi-rank run with the exchange behind the C ABI (transport="c"); None, or a halo of one rank: no ghost update.
+        The stage vectors live in a workspace of the operator, allocated by the first call."""
+        n = self.mesh.num_cells
+        if not (isinstance(u_local, torch.Tensor) and u_local.is_cuda and u_local.dtype == torch.float64 and u_local.is_contiguous()
+                and u_local.numel() == 3 * n):
+            raise RDyHipError(83, f"u_local must be a contiguous float64 device tensor of {n} cells x 3")
+        h = getattr(halo, "_halo", None) if halo is not None else None
+        if halo is not None and h is None and getattr(halo, "world", 1) > 1:
+            raise RDyHipError(83, 'rk4_step needs a halo with the exchange behind the C ABI (HaloExchange(transport="c"))')
+        self._last_state = None      # the state of the last evaluation is the operator's own stage array
+        _lib.check(_lib.load().rdyhip_rk4_step(self._h, h, float(dt), _ptr(u_local), _stream()))
+
     # -- second order: ComputeLeastSquaresGradients for the owned cells (src/operator_fluxes_ceed.c:998-1042)
     def compute_gradients(self, u_local: torch.Tensor, phase: int = PHASE_ALL):
         _lib.check(_lib.load().rdyhip_compute_gradients(self._h, int(phase), _ptr(u_local), _stream()))

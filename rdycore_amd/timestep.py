@@ -10,7 +10,10 @@ evaluations, with the state kept on the GPU.
   * classical Runge-Kutta (`temporal="rk4"`: the reference's `numerics.temporal: rk4` = TSRK with TSRK4,
     src/rdysetup.c:1187-1189): four RHS evaluations per step on the stage states U, U + dt/2 k1, U + dt/2 k2, U + dt k3
     -- each one OperatorRHSFunction with its ghost update and the FULL step's dt in the friction term (TSGetTimeStep,
-    src/rdysetup.c:1129) -- then U += dt/6 (k1 + 2 k2 + 2 k3 + k4).  Stage vectors stay on the device.
+    src/rdysetup.c:1129) -- then U += dt/6 (k1 + 2 k2 + 2 k3 + k4).  Stage vectors stay on the device.  `fused=True`
+    (default) takes the whole step in one call behind the C ABI (rdyhip_rk4_step: one launch per stage state, one for the
+    final combination) where the operator has it and the halo, if any, is exchanged there too; `fused=False` keeps the
+    loop of RHS, copy and axpy calls.  Both give the same bits.
   * RDyAdvance (src/rdyadvance.c:261-383): advance to the next coupling time
     with the last step shortened to land on it (TS_EXACTFINALTIME_MATCHSTEP),
     and, when adaptive time stepping is on, rescale dt from the previous
@@ -142,6 +145,12 @@ class EulerStepper:
     def _rk4_step(self, h: float, u_local: torch.Tensor):
         """TSStep_RK with the TSRK4 tableau (A = [[0], [1/2], [0, 1/2], [0, 0, 1]], b = [1/6, 1/3, 1/3, 1/6]): every stage
         is one OperatorRHSFunction on the stage state; the diagnostics left behind are the last stage's, as in the reference"""
+        if self.fused and hasattr(self.op, "rk4_step"):
+            # the whole step behind the C ABI, unless the ghost update is driven from Python (transport="torch")
+            if self.halo is None or self.halo.world == 1:
+                return self.op.rk4_step(h, u_local)
+            if getattr(self.halo, "_halo", None) is not None:
+                return self.op.rk4_step(h, u_local, halo=self.halo)
         no = self.op.mesh.num_owned_cells
         if self._stage is None or self._stage[0].shape != u_local.shape:
             self._stage = [torch.empty_like(u_local)] + [torch.empty((no, 3), dtype=torch.float64, device=u_local.device) for _ in range(4)]
