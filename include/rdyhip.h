@@ -553,6 +553,50 @@ int rdyhip_euler_step(RDyHipOperator op, int32_t phase, int32_t flags, double dt
  * owns nothing still takes part in the four exchanges. */
 int rdyhip_rk4_step(RDyHipOperator op, RDyHipHalo halo /* may be NULL */, double dt, double *u_local, void *stream);
 
+/* ---- time-averaged output fields -----------------------------------------------
+ * WriteXDMFOutput's three OutputVars (src/xdmf_output.c:436-504) -- the solution, the primitive variables
+ * (op->primitive_variables, src/rdysetup.c:1535-1542) and the sources (op->src_inst, the copy of the external sources that
+ * ApplyPetscOperator takes, src/operator.c:668-669) -- accumulated on the device:
+ *   rdyhip_output_mean_accumulate  AccumulateOutputVar (196-206): accumulated_time += dt; VecAXPY(accum, dt, inst), once per step
+ *   rdyhip_output_mean_get         ComputeMean (211-230): mean = accum * (1 / accumulated_time), at an output
+ *   rdyhip_output_mean_reset       ResetOutputVar (233-241): accum = 0, accumulated_time = 0
+ * `vars` is a mask of RDYHIP_OUTPUT_*; every variable has its own [num_owned_cells][3] accumulator and its own time.
+ *   - _enable allocates a zeroed accumulator for each named variable that has none yet (an existing one keeps its content);
+ *     the bytes are counted in RDyHipLayoutInfo.device_bytes and freed by rdyhip_destroy.  The only call of the five that
+ *     may synchronise the device.
+ *   - _accumulate enqueues ONE launch on `stream` for all of `vars` and adds dt to the host-side time of each:
+ *       solution             u_local, device, [num_cells][3]: the state to average; needed only with RDYHIP_OUTPUT_SOLUTION.
+ *       primitive variables  those of "the u_local of the most recent evaluation" as defined for rdyhip_field_ptr (for
+ *                            rdyhip_euler_step its INPUT state, after rdyhip_rk4_step the operator's stage state; before any
+ *                            evaluation the zeros of rdyhip_create).  While the evaluations do not store them they are formed
+ *                            in the launch from that array, with the arithmetic of the kernels (the same bits a storing launch
+ *                            writes), so the array must still hold that state and work that wrote it must be ordered before
+ *                            `stream`'s; a pointer the runtime no longer knows as memory of the operator's device gives
+ *                            RDYHIP_ERR_USER, nothing is launched and no time is added.  While they are stored (a pointer is
+ *                            out) the stored rows are read -- whatever they hold: after a rdyhip_field_ptr that itself failed
+ *                            with "the state array of the last evaluation is gone", they are those of the last storing
+ *                            evaluation until the next evaluation writes them, and this call sums them without complaint.  Either way the call leaves the storing as it is: a host that
+ *                            never takes the pointer keeps its evaluations free of the 24 B/cell store.
+ *       sources              the operator's own [owned][3] array, read at the call's place in `stream` -- NOT at the
+ *                            evaluation, where the reference takes its snapshot.  A host that changes the forcing between the
+ *                            evaluation and the accumulate orders the two itself.  The water-only mode of the source
+ *                            (rdyhip_set_external_source) is neither needed nor ended.
+ *     A variable that is not enabled: RDYHIP_ERR_USER, no time changes.  A rank that owns nothing: the times advance, nothing
+ *     is launched.  The sums are fused multiply-adds, the bits of rdyhip_axpy_owned(dt, inst, accum).
+ *   - _get writes the mean of exactly one variable into d_mean (device, [num_owned_cells][3]) on `stream` and reports the
+ *     accumulated time through `accumulated_time` if that is not NULL; it resets nothing.  No accumulated time:
+ *     RDYHIP_ERR_USER, as the PetscCheck of ComputeMean (213).
+ *   - _reset zeroes the named accumulators on `stream` and their times; _time reports the time of one variable.
+ * Every argument error (null operator, unknown bits, a null array where one is needed) is reported before any device call. */
+#define RDYHIP_OUTPUT_SOLUTION 1
+#define RDYHIP_OUTPUT_PRIMITIVE_VARIABLES 2
+#define RDYHIP_OUTPUT_SOURCES 4
+int rdyhip_output_mean_enable(RDyHipOperator op, int32_t vars);
+int rdyhip_output_mean_accumulate(RDyHipOperator op, int32_t vars, double dt, const double *u_local, void *stream);
+int rdyhip_output_mean_get(RDyHipOperator op, int32_t var, double *d_mean, double *accumulated_time, void *stream);
+int rdyhip_output_mean_reset(RDyHipOperator op, int32_t vars, void *stream);
+int rdyhip_output_mean_time(RDyHipOperator op, int32_t var, double *accumulated_time);
+
 /* ---- introspection ----------------------------------------------------------
  * numbers describing the device layout, for DESIGN.md / bench.py */
 typedef struct {

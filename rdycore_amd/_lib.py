@@ -100,6 +100,11 @@ SYMBOLS = {
     "rdyhip_axpy_owned": (C.c_int, [_H, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rdyhip_euler_step": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rdyhip_rk4_step": (C.c_int, [_H, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
+    "rdyhip_output_mean_enable": (C.c_int, [_H, C.c_int32]),
+    "rdyhip_output_mean_accumulate": (C.c_int, [_H, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]),
+    "rdyhip_output_mean_get": (C.c_int, [_H, C.c_int32, C.c_void_p, c_double_p, C.c_void_p]),
+    "rdyhip_output_mean_reset": (C.c_int, [_H, C.c_int32, C.c_void_p]),
+    "rdyhip_output_mean_time": (C.c_int, [_H, C.c_int32, c_double_p]),
     "rdyhip_halo_create": (C.c_int, [_H, C.c_void_p, C.c_int32, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p, C.POINTER(C.c_void_p)]),
     "rdyhip_halo_destroy": (C.c_int, [C.POINTER(C.c_void_p)]),
     "rdyhip_halo_overlaps": (C.c_int32, [C.c_void_p]),

@@ -28,6 +28,7 @@ WELL_BALANCING_HR = 2        # hydrostatic reconstruction
 LIMITER_MINMOD, LIMITER_NONE, LIMITER_VANLEER = 0, 1, 2   # RDyLimiterType, include/private/rdyconfigimpl.h:64-71
 
 PHASE_ALL, PHASE_INTERIOR, PHASE_HALO = 0, 1, 2
+OUTPUT_SOLUTION, OUTPUT_PRIMITIVE_VARIABLES, OUTPUT_SOURCES = 1, 2, 4   # RDYHIP_OUTPUT_*: the time-averaged output fields
 
 
 @dataclasses.dataclass
@@ -226,6 +227,40 @@ class Operator:
             raise RDyHipError(83, 'rk4_step needs a halo with the exchange behind the C ABI (HaloExchange(transport="c"))')
         self._last_state = None      # the state of the last evaluation is the operator's own stage array
         _lib.check(_lib.load().rdyhip_rk4_step(self._h, h, float(dt), _ptr(u_local), _stream()))
+
+    # -- time-averaged output fields (WriteXDMFOutput's OutputVars, src/xdmf_output.c:196-241, 436-504) ------------------
+    def enable_output_means(self, vars: int):
+        """rdyhip_output_mean_enable: a zeroed [owned,3] accumulator for each of OUTPUT_SOLUTION | OUTPUT_PRIMITIVE_VARIABLES |
+        OUTPUT_SOURCES in `vars` that has none yet."""
+        _lib.check(_lib.load().rdyhip_output_mean_enable(self._h, int(vars)))
+
+    def accumulate_output_means(self, vars: int, dt: float, u_local: Optional[torch.Tensor] = None):
+        """AccumulateOutputVar for all of `vars` in one launch on the current stream (rdyhip_output_mean_accumulate): the
+        solution from `u_local` ([num_cells,3], needed only with OUTPUT_SOLUTION), the primitive variables of the most recent
+        evaluation and the operator's source array; the evaluations go on not storing the primitive variables."""
+        if u_local is not None:
+            n = self.mesh.num_cells
+            if not (isinstance(u_local, torch.Tensor) and u_local.is_cuda and u_local.dtype == torch.float64 and u_local.is_contiguous()
+                    and u_local.numel() == 3 * n):
+                raise RDyHipError(83, f"u_local must be a contiguous float64 device tensor of {n} cells x 3")
+        _lib.check(_lib.load().rdyhip_output_mean_accumulate(self._h, int(vars), float(dt), _ptr(u_local) if u_local is not None else None,
+                                                            _stream()))
+
+    def output_mean(self, var: int):
+        """ComputeMean of one variable (rdyhip_output_mean_get): (mean [owned,3], accumulated time); nothing is reset."""
+        out = torch.empty((self.mesh.num_owned_cells, 3), dtype=torch.float64, device="cuda")
+        t = C.c_double()
+        _lib.check(_lib.load().rdyhip_output_mean_get(self._h, int(var), _ptr(out), C.byref(t), _stream()))
+        return out, t.value
+
+    def reset_output_means(self, vars: int):
+        """ResetOutputVar (rdyhip_output_mean_reset): accumulators and times of `vars` back to zero, on the current stream"""
+        _lib.check(_lib.load().rdyhip_output_mean_reset(self._h, int(vars), _stream()))
+
+    def output_mean_time(self, var: int) -> float:
+        t = C.c_double()
+        _lib.check(_lib.load().rdyhip_output_mean_time(self._h, int(var), C.byref(t)))
+        return t.value
 
     # -- second order: ComputeLeastSquaresGradients for the owned cells (src/operator_fluxes_ceed.c:998-1042)
     def compute_gradients(self, u_local: torch.Tensor, phase: int = PHASE_ALL):

@@ -14,6 +14,9 @@ evaluations, with the state kept on the GPU.
     (default) takes the whole step in one call behind the C ABI (rdyhip_rk4_step: one launch per stage state, one for the
     final combination) where the operator has it and the halo, if any, is exchanged there too; `fused=False` keeps the
     loop of RHS, copy and axpy calls.  Both give the same bits.
+  * time-averaged output (`means`: a mask of the operator's OUTPUT_* bits): what the TS monitor does around TSSolve for
+    WriteXDMFOutput's OutputVars (src/xdmf_output.c:436-504) -- one accumulate of dt x (solution, primitive variables,
+    sources) for the initial state and one after every step, on the device (rdyhip_output_mean_accumulate).
   * RDyAdvance (src/rdyadvance.c:261-383): advance to the next coupling time
     with the last step shortened to land on it (TS_EXACTFINALTIME_MATCHSTEP),
     and, when adaptive time stepping is on, rescale dt from the previous
@@ -65,7 +68,14 @@ class AdaptiveTime:
 class EulerStepper:
     """the explicit TS of RDyAdvance: forward Euler (default) or, with temporal="rk4", classical Runge-Kutta"""
 
-    def __init__(self, op, halo=None, adaptive: Optional[AdaptiveTime] = None, fused: bool = True, forcing=None, temporal: str = "euler"):
+    def __init__(self, op, halo=None, adaptive: Optional[AdaptiveTime] = None, fused: bool = True, forcing=None, temporal: str = "euler",
+                 means: int = 0):
+        """`means`: which time-averaged output fields to keep (OUTPUT_SOLUTION | OUTPUT_PRIMITIVE_VARIABLES | OUTPUT_SOURCES of
+        rdycore_amd.operator; 0: none, and none of the operator's output-mean calls is made).  With bits set the stepper
+        accumulates once before the first step of its life -- the initial state, whatever the primitive variables and the
+        sources hold then -- and once after every step.  Every accumulate is weighted with the INTERVAL's dt, also after a
+        last step that was shortened to land on the interval's end: the reference does the same
+        (AccumulateOutputVar(.., rdy->dt), src/xdmf_output.c:452-456).  output_mean() returns a mean and starts a new window."""
         if temporal not in ("euler", "rk4"):
             raise ValueError(f"temporal = {temporal!r}: the explicit path has euler and rk4 (include/private/rdyconfigimpl.h:110-115)")
         self.temporal = temporal
@@ -86,6 +96,16 @@ class EulerStepper:
         self.max_courant = None      # diagnostics of the last interval, all ranks (None = not updated yet)
         self.courant = None          # the whole struct (value + global edge / cell id of the maximum)
         self._f = None
+        self.means = int(means)
+        if self.means:
+            op.enable_output_means(self.means)
+
+    def output_mean(self, var: int):
+        """ComputeMean + ResetOutputVar (src/xdmf_output.c:211-241) of one variable: (mean [owned,3], accumulated time); the
+        variable's next window starts empty"""
+        mean, t = self.op.output_mean(var)
+        self.op.reset_output_means(var)
+        return mean, t
 
     def rhs(self, dt, u_local, f_global):
         if self.halo is not None and self.halo.world > 1:
@@ -117,10 +137,15 @@ class EulerStepper:
         cur = u_local
         if self.fused and (self._u2 is None or self._u2.shape != u_local.shape):
             self._u2 = torch.empty_like(u_local)
+        m = self.means
+        if m and self.step == 0:
+            self.op.accumulate_output_means(m, dt, u_local)      # the monitor's call at step 0
         while self.time < t_end * (1.0 - 1e-14):
             h = min(dt, t_end - self.time)       # TS_EXACTFINALTIME_MATCHSTEP
             if self.temporal == "rk4":
                 self._rk4_step(h, u_local)
+                if m:
+                    self.op.accumulate_output_means(m, dt, u_local)
             elif self.fused:
                 nxt = self._u2 if cur is u_local else u_local
                 if self.halo is not None and self.halo.world > 1:
@@ -128,9 +153,16 @@ class EulerStepper:
                 else:
                     self.op.euler_step(h, cur, nxt)   # resets the Courant diagnostic like every RHS (src/rdysetup.c:1136)
                 cur = nxt
+                if m:
+                    self.op.accumulate_output_means(m, dt, nxt)   # solution: the step's output; primitive variables: of its input
             else:
                 self.rhs(h, u_local, self._f)
+                if m & 6:
+                    # the primitive variables belong to the state the RHS saw: before the axpy rewrites it in place
+                    self.op.accumulate_output_means(m & 6, dt)
                 self.op.axpy_owned(h, self._f, u_local)
+                if m & 1:
+                    self.op.accumulate_output_means(1, dt, u_local)
             self.time += h
             self.step += 1
         if cur is not u_local:
