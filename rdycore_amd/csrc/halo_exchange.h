@@ -65,8 +65,6 @@ struct RDyHipHalo_s {
     ++step;
   }
   ~RDyHipHalo_s() {
-    d_send_ids.release(); d_recv_ids.release(); d_send.release(); d_recv.release(); d_send_tile_off.release(); d_send_ent.release();
-    d_gsend_off.release(); d_gsend_rows.release();
     for (auto &c : choice)
       for (int i = 0; i < 2 * FormChoice::TRIAL; ++i) {
         if (c.ev0[i]) (void)hipEventDestroy(c.ev0[i]);
@@ -506,8 +504,6 @@ static int halo_attach_send_lists(RDyHipHalo h, bool on) {
       if (!(tiles[(size_t)ent[i].first].cnt & TILE_HALO_FLAG)) h->send_cells_in_halo_tiles = false;
     }
     for (int32_t t = 0; t < op->ntiles; ++t) off[(size_t)t + 1] += off[t];
-    h->d_send_tile_off.release();
-    h->d_send_ent.release();
     int rc = h->d_send_tile_off.upload(off);
     if (!rc) rc = h->d_send_ent.upload(packed);
     if (rc) return rc;
@@ -537,8 +533,6 @@ static int halo_attach_send_lists(RDyHipHalo h, bool on) {
         const int32_t o = op->prefix ? c : op->h_l2o[(size_t)c];
         rows[(size_t)fill[(size_t)pos[(size_t)o]]++] = i;
       }
-      h->d_gsend_off.release();
-      h->d_gsend_rows.release();
       int rc = h->d_gsend_off.upload(off);
       if (!rc) rc = h->d_gsend_rows.upload(rows);
       if (rc) return rc;

@@ -60,7 +60,6 @@ struct MusclArgs {
   const uint16_t *bn_idx;   // [halo entries][4] LDS slot of each first-ring cell's s-th neighbour; BN_NONE: no neighbour in that
                             //                   slot; BN_GLOBAL: a ghost cell, its gradient comes from `grad` (exchanged)
 };
-constexpr uint16_t BN_NONE = 0xFFFF, BN_GLOBAL = 0xFFFE;
 
 // LDS layout of the second-order kernel: one plane per value with COMPILE-TIME plane strides -- the plane offsets are
 // instruction immediates (no register, no address arithmetic) and every read is a full-rate ds_read_b64.  Every tile is cut
@@ -81,14 +80,13 @@ struct MusclSoA {
 // gradients, dead by then.  The plane strides are deliberately NOT multiples of 64 doubles: hipcc would otherwise fuse the
 // reads of two planes into ds_read2st64_b64, which is served like ds_read2_b64.
 // (every ring cell is staged by one thread: at most TILE of them; the state planes keep 8 slots of slack so that their stride
-// is no multiple of 64 doubles)
-constexpr int MUSCL_MAX_RING1_TRI = TILE_MAX_HALO_TRI, MUSCL_MAX_RING_TRI = TILE;
+// is no multiple of 64 doubles; the capacities MUSCL_MAX_RING*: tile_format.h)
 using MusclSoATri = MusclSoA<TILE + MUSCL_MAX_RING_TRI + 8, TILE + MUSCL_MAX_RING1_TRI, TILE_MAX_REC + 8>;
 static_assert(MUSCL_MAX_RING_TRI <= TILE, "one thread stages one ring cell");
 // quads / mixed meshes: <= 112 first-ring cells, <= 168 ring cells in all; 37 664 B per workgroup
-constexpr int MUSCL_MAX_RING1_QUAD = TILE_MAX_HALO_QUAD, MUSCL_MAX_RING_QUAD = 168;
 using MusclSoAQuad = MusclSoA<TILE + MUSCL_MAX_RING_QUAD, TILE + MUSCL_MAX_RING1_QUAD, TILE_MAX_REC + 8>;
 static_assert(MUSCL_MAX_RING_QUAD <= TILE && TILE_MAX_HALO_QUAD <= TILE && TILE_MAX_HALO_TRI <= TILE, "one thread stages one ring / halo cell");
+static_assert(muscl_lds_bytes(3) == MusclSoATri::lds_bytes && muscl_lds_bytes(4) == MusclSoAQuad::lds_bytes, "the host sizes the launch from tile_format.h");
 #define MSQ(k, j) sq[LAY::qidx((k), (j))]
 #define MSG(k, j) sg[LAY::gidx((k), (j))]
 #define MEF(c, e) ef[LAY::eidx((c), (e))]

@@ -1,0 +1,177 @@
+// What an operator is made of: the device buffers that free themselves, the staging ring of the stream-ordered setters and
+// RDyHipOperator_s.  Includes the HIP runtime and host_layout.h (for LayoutCounts); included by rdyhip_api.hip only.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <vector>
+
+#include "rdyhip.h"
+#include "error.h"
+#include "host_layout.h"
+#include "swe_kernels.h"
+
+using namespace rdyhip;
+
+#define HIP_TRY(expr)                                                                                       \
+  do {                                                                                                      \
+    hipError_t e_ = (expr);                                                                                 \
+    if (e_ != hipSuccess) return fail(RDYHIP_ERR_LIB, "%s failed: %s", #expr, hipGetErrorString(e_));       \
+  } while (0)
+
+// A device array that frees itself.  alloc / upload / zeros on a buffer that holds memory release it first.
+template <typename T>
+struct DevBuf {
+  T     *p = nullptr;
+  size_t n = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr, o.n = 0; }
+  DevBuf &operator=(DevBuf &&o) noexcept {
+    if (this != &o) {
+      release();
+      p = o.p, n = o.n;
+      o.p = nullptr, o.n = 0;
+    }
+    return *this;
+  }
+  ~DevBuf() { release(); }
+  int alloc(size_t count) {
+    release();
+    const size_t bytes = (count ? count : 1) * sizeof(T);
+    hipError_t   e     = hipMalloc((void **)&p, bytes);
+    if (e != hipSuccess) {
+      p = nullptr;
+      return fail(RDYHIP_ERR_MEM, "hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
+    }
+    n = count;
+    return 0;
+  }
+  // room for `count` elements: grows only, and the content is not kept
+  int reserve(size_t count) { return p && n >= count ? 0 : alloc(count); }
+  int upload(const std::vector<T> &h) {
+    int rc = alloc(h.size());
+    if (rc) return rc;
+    if (!h.empty()) HIP_TRY(hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+    return 0;
+  }
+  int zeros(size_t count) {
+    int rc = alloc(count);
+    if (rc) return rc;
+    HIP_TRY(hipMemset(p, 0, (count ? count : 1) * sizeof(T)));
+    return 0;
+  }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    n = 0;
+  }
+  size_t bytes() const { return n * sizeof(T); }
+};
+
+// Staging of the stream-ordered setters (rdyhip_set_*_on): a small ring of slots, each a pinned host buffer + a device
+// buffer + an event.  The caller's array is copied into the pinned buffer before the call returns (the caller may reuse it
+// at once, as with the reference's setters, which copy into a Vec); the host -> device copy then runs on the operator's own
+// copy stream, beside whatever the caller's stream is executing, and only the final scatter into the operator's field is
+// ordered on the caller's stream.  A slot is reused once the work that read it has finished (its event).
+struct StageRing {
+  static constexpr int N = 4;
+  struct Slot {
+    void      *h = nullptr, *d = nullptr;
+    size_t     cap = 0;
+    hipEvent_t copied = nullptr, done = nullptr;
+    bool       used = false;
+  } slot[N];
+  int         next = 0;
+  hipStream_t copy = nullptr;
+  StageRing() = default;
+  StageRing(const StageRing &) = delete;
+  StageRing &operator=(const StageRing &) = delete;
+  ~StageRing() { release(); }
+  void release() {
+    for (auto &s : slot) {
+      if (s.h) (void)hipHostFree(s.h);
+      if (s.d) (void)hipFree(s.d);
+      if (s.copied) (void)hipEventDestroy(s.copied);
+      if (s.done) (void)hipEventDestroy(s.done);
+      s = Slot{};
+    }
+    if (copy) (void)hipStreamDestroy(copy);
+    copy = nullptr;
+  }
+};
+
+struct RDyHipHalo_s;
+// (the layout's numbers -- n_cells, n_owned, S, K, n_halo, ntiles, ... -- are the base class's, copied from HostLayout::counts)
+struct RDyHipOperator_s : LayoutCounts {
+  StageRing stage;
+  RDyHipConfig config;
+  RDyHipHalo_s *fused_halo = nullptr;  // the halo whose send lists are attached to the tile descriptors (rdyhip_halo_fuse_pack)
+  std::vector<int32_t> h_l2o;          // local -> owned cell id, kept only when the owned cells are not a prefix
+  int          device = 0;
+  int32_t      n_internal = 0;
+  int64_t      stride = 0;
+  int          grid = 0, xcd_chunks = 0;        // cell kernel
+  int          pgrid = 0, tiled_xcd_chunks = 0; // tiled (persistent) kernel
+  int          interior_shrink = 32;            // the INTERIOR phase leaves 1/interior_shrink of the workgroup slots free (0: none)
+  bool         balance_rounds = false;          // size the persistent grid so that all workgroups walk the same number of tiles
+  bool         keep_fdiv = false;
+
+  DevBuf<int32_t> d_o2l, d_nbr, d_pos, d_halo_list, d_btype, d_bleft, d_bghost_list;
+  DevBuf<double>  d_cn, d_sn, d_coef, d_dzdx, d_dzdy, d_mannings, d_extsrc;
+  // The water source by itself, [n_owned]: a mirror of component 0 of d_extsrc (which stays the canonical array and is always
+  // current), kept by every writer of the source while src_water_only holds.  The first-order / HR tiled kernels then read
+  // it instead of the 24-B rows: 8 B of HBM traffic per cell where a read of any part of a row costs all 24.
+  DevBuf<double>  d_src_water;
+  bool            src_water_only = true;   // every momentum source is +0.0 and the plane is current
+  bool            src_escaped    = false;  // rdyhip_field_ptr handed out d_extsrc: it may be written behind our back, for good
+  DevBuf<double>  d_bvalues, d_bflux, d_baccum, d_bcn, d_bsn, d_pv, d_fdiv, d_blk_max;
+  // The primitive variables are stored by the evaluations only once somebody can look at them (rdyhip_field_ptr, until
+  // rdyhip_field_release); the first request after evaluations that did not store derives them from the state of the last one.
+  bool            pv_wanted  = false;    // d_pv has been handed out: every launch stores
+  bool            pv_pending = false;    // at least one evaluation since the last store did not store
+  const double   *pv_u       = nullptr;  // u_local of the most recent evaluation that did not store ...
+  hipStream_t     pv_stream  = nullptr;  // ... and the caller's stream it was enqueued on
+  DevBuf<int32_t> d_blk_pos;
+  DevBuf<DeviceCourant> d_courant;
+  DevBuf<ColdArgs>      d_cold;   // the kernels' rarely read pointers (swe_kernels.h), written once at create
+  int32_t n_bghost = 0;
+  // tiled kernel (swe_kernels.h)
+  bool             use_tiled = true;
+  bool             hr = false;   // hydrostatic reconstruction
+  bool             uout_cached = false;  // Euler-step kernels store u_out with the default cache policy: the state fits the Infinity Cache
+  DevBuf<double>   d_zc_local;
+  DevBuf<TileDesc> d_tiles;
+  DevBuf<uint32_t> d_e_lr;
+  DevBuf<int32_t>  d_hcells, d_tile_bk, d_tile_boff, d_halo_tiles, d_e_pos, d_x_lr;
+  DevBuf<uint32_t> d_x_flags;
+  DevBuf<double>   d_x_cs, d_x_cfac, d_x_mid;
+  int32_t          n_xedges = 0;
+  std::vector<int32_t> h_tile_c0;  // [ntiles + 1] first owned cell of each tile (the fused pack's send lists are built per tile)
+  DevBuf<double>   d_e_cs;
+  DevBuf<uint16_t> d_slot_ref;   // S == 4
+  DevBuf<uint32_t> d_slot_ref3;  // S == 3
+  // second order (muscl_kernels.h)
+  DevBuf<double>   d_grad, d_e_mid, d_cxy;
+  DevBuf<int32_t>  d_hcells2, d_c_off;
+  DevBuf<uint16_t> d_bn_idx;
+  int              pgrid_muscl = 0;
+
+  // host copies needed to resolve the Courant position into ids
+  std::vector<int32_t> h_internal_edge, h_edge_cells, h_bedge, h_boff;
+  std::vector<int64_t> h_cell_gid, h_edge_gid;
+  std::vector<double>  h_area;
+  RDyHipCourant        courant{0.0, -1, -1};
+  // staging buffers for the setters
+  DevBuf<double>  d_scratch_f;   // F of rdyhip_euler_step when the caller wants none and the kernel cannot skip it
+  DevBuf<double>  d_stage_vals;
+  DevBuf<int32_t> d_stage_ids;
+  // rdyhip_rk4_step: the stage state [n_cells][3] and k1..k4 [n_owned][3], allocated by the first call, kept until destroy
+  DevBuf<double>  d_rk_y, d_rk_k[4];
+  bool            rk_ready = false;
+  // rdyhip_output_mean_*: one [n_owned][3] accumulator per enabled variable (bit i of RDYHIP_OUTPUT_*) and the time it spans
+  DevBuf<double>  d_out_acc[3];
+  double          out_time[3] = {0.0, 0.0, 0.0};
+
+  int64_t device_bytes = 0;
+};

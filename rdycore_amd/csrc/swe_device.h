@@ -7,20 +7,18 @@
 // pow(x,0.5), pow(x,+-k/3) and IEEE division, with divisions that share a
 // denominator sharing one reciprocal.  All of it stays ~1e-15 relative; the
 // parity bar is 1e-10 (tests/test_gpu_parity.py).  A cell's edge contributions
-// are summed in the reference's edge-loop order (slot ordering, rdyhip_api.hip).
+// are summed in the reference's edge-loop order (slot ordering, host_layout.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "tile_format.h"
 
 namespace rdyhip {
 
 // src/swe/swe_types_petsc.h:7
 constexpr double GRAVITY      = 9.806;
 constexpr double SQRT_GRAVITY = 3.1314533367112465;  // sqrt(9.806) correctly rounded
-
-constexpr int32_t NBR_EMPTY = INT32_MIN;    // unused slot (triangle in a 4-slot layout)
-constexpr int32_t NBR_GHOST = 1 << 30;      // neighbour is a ghost (non-owned) cell
-constexpr int32_t NBR_MASK  = (1 << 30) - 1;
 
 // Reciprocal by v_rcp_f64 + two Newton steps (the same refinement the IEEE
 // division expansion performs, without its scaling / fix-up wrapper): <= 1 ulp

@@ -5,7 +5,7 @@
 //
 //  * swe_rhs_tiled_kernel (default): one workgroup = one tile of up to 256
 //    consecutive owned cells (cut at create so that a tile's edge records and
-//    halo cells fit fixed capacities: rdyhip_api.hip, layout_build_tiles).
+//    halo cells fit fixed capacities: host_layout.h, layout_build_tiles).
 //      phase 0  every thread loads its cell's state, derives the Riemann side
 //               data (velocities, sqrt(h), sqrt(g h)) once and stages it in LDS;
 //      phase 1  threads sweep the tile's edge list (every edge that touches a
@@ -31,15 +31,7 @@
 
 namespace rdyhip {
 
-constexpr int BLOCK = 256;  // threads per workgroup of the cell-centric kernel
-constexpr int TILE = 256;   // threads per workgroup of the tiled kernels = the largest number of cells in a tile (a multiple of 64)
-// Capacities every tile is cut to at create (layout_build_tiles): edge records = two register-resident rounds of the edge
-// phase; halo cells (cells outside the tile that share an edge with it) per slots-per-cell flavour.  The LDS planes have
-// these compile-time lengths, so every plane offset is an instruction immediate.
-constexpr int TILE_MAX_REC = 2 * TILE;
-constexpr int TILE_MAX_HALO_TRI = 104, TILE_MAX_HALO_QUAD = 112;
-
-constexpr uint16_t SLOT_EMPTY = 0xFFFF;
+// (BLOCK, TILE, the capacities every tile is cut to, the packed edge records and TileDesc: tile_format.h)
 
 // Data that is streamed through exactly once per launch -- the per-cell streams (flux coefficients, bed slopes,
 // Manning n, external source), the tile edge records and the outputs F / primitive variables -- is loaded and
@@ -62,8 +54,6 @@ struct DeviceCourant {
 // workgroup), the cell-centric kernel's neighbour tables -- lives in a device-resident ColdArgs block, written once at
 // create and read through ONE pointer with scalar loads at the point of use (RDY_COLD), so that it occupies no register
 // on the hot path.  (Round 2 passed all ~40 pointers by value: 51-83 SGPRs spilled to VGPR lanes per instantiation.)
-struct TileDesc;
-
 struct ColdArgs {
   const int32_t *nbr;        // [S][stride] neighbour ids (cell kernel, gradient kernel)
   const double  *cn, *sn;    // [S][stride] (cell kernel)
@@ -401,25 +391,8 @@ __device__ __forceinline__ void store_boundary_flux(const KernelArgs &a, int k, 
 }
 
 // ---------------------------------------------------------------------------
-// tiled kernel
+// tiled kernel (the packed edge records EDGE_*, REF3_EMPTY and the tile descriptor: tile_format.h)
 // ---------------------------------------------------------------------------
-// packed end points of a tile edge: LDS slot of the left cell | slot of the
-// right cell << 11 | EDGE_BOUNDARY.  Slots 0..255 are the tile's own cells,
-// 256.. the tile's halo cells (cells outside the tile that share an edge with
-// it).  For a boundary edge the right field is the index into the tile's
-// boundary-edge list.
-constexpr uint32_t EDGE_SLOT_MASK = 0x7FF;
-constexpr int      EDGE_R_SHIFT   = 11;
-constexpr uint32_t EDGE_BOUNDARY  = 1u << 22;
-// The unit normal (cn, sn) is stored as ONE double: the component of smaller
-// magnitude; the other is +-sqrt(1 - cs^2) (well conditioned: cs^2 <= 1/2).
-constexpr uint32_t EDGE_CS_IS_CN     = 1u << 23;  // the stored component is cn (else sn)
-constexpr uint32_t EDGE_OTHER_NEG    = 1u << 24;  // the reconstructed component is negative
-// second order: the edge belongs to another rank (edges.is_owned = false): ApplyInteriorFlux2R evaluates its Courant number
-// there (swe_petsc.c:172-190); here its flux still feeds the owned cell, its wave speed is kept out of the diagnostic
-constexpr uint32_t EDGE_NOT_OWNED    = 1u << 25;
-// slot references of a triangle mesh (S == 3): 3 x 10 bits in one uint32, 0x3FF = unused
-constexpr uint32_t REF3_EMPTY = 0x3FF;
 
 // index of slot s's edge in the tile's edge list, or -1 for an unused slot.  r0 (, r1): the cell's slot references
 // (KernelArgs::slot_ref): triangles three 10-bit ones in r0, quads four 16-bit ones in r0, r1.  (The first-order kernel's
@@ -442,21 +415,6 @@ __device__ __forceinline__ void edge_normal(uint32_t lr, double cs, double &cn, 
   cn               = is_cn ? cs : other;
   sn               = is_cn ? other : cs;
 }
-
-struct TileDesc {  // 16 B, one per tile (+1 sentinel): everything about a tile in ONE scalar load of four registers
-  int32_t  e_off;  // first edge record
-  int32_t  h_off;  // first halo-cell entry
-  int32_t  c_off;  // first owned cell (the tile's cells are c_off .. c_off + nc() - 1; a multiple of 16 wherever the numbering allows)
-  uint32_t cnt;    // edge records (bits 0-10) | halo cells (bits 11-21) | cells - 1 (bits 22-29) | bit 30: a tile cell is sent to
-                   // another rank (set while a halo with the fused pack is attached) | bit 31: a tile cell has a ghost neighbour
-  __host__ __device__ int  ne() const { return (int)(cnt & 0x7FFu); }
-  __host__ __device__ int  nh() const { return (int)((cnt >> 11) & 0x7FFu); }
-  __host__ __device__ int  nc() const { return (int)((cnt >> 22) & 0xFFu) + 1; }
-  __host__ __device__ bool halo() const { return (cnt >> 31) != 0; }
-  __host__ __device__ bool send() const { return ((cnt >> 30) & 1u) != 0; }
-};
-constexpr uint32_t TILE_HALO_FLAG = 1u << 31;
-constexpr uint32_t TILE_SEND_FLAG = 1u << 30;
 
 // The fused pack: the lanes of a wave hand the new state of the tile's send cells to the send buffer.  Every wave scans the
 // tile's (short) entry list 64 entries at a time and takes the entries whose cell it holds; the values come from the owning
@@ -639,10 +597,6 @@ __device__ __forceinline__ void courant_extra_edges(const KernelArgs &a, double 
   }
 }
 
-constexpr int TILED_NS_TRI = TILE + TILE_MAX_HALO_TRI, TILED_NS_QUAD = TILE + TILE_MAX_HALO_QUAD, TILED_NE = TILE_MAX_REC + 8;
-constexpr size_t tiled_lds_bytes(int S, bool hr) {
-  return sizeof(double) * ((hr ? 6 : 5) * (size_t)(S == 3 ? TILED_NS_TRI : TILED_NS_QUAD) + 2 * (size_t)TILE + (hr ? 6 : 4) * (size_t)TILED_NE);
-}
 // Workgroups per CU (= waves per SIMD: a workgroup is one wave on each of the four SIMDs) of a (S, SRC, HR) family.  The
 // persistent grid is sized once per operator and every call form runs on it, so all six OVW / EULER / FNT instantiations
 // of a family share the setting.  Four needs <= 128 VGPRs and 4 x tiled_lds_bytes <= 160 KB: the HR workgroup (46 KB) cannot,

@@ -467,7 +467,7 @@ def hilbert_cell_order(centroids: np.ndarray) -> np.ndarray:
     """Permutation that sorts cells along a Hilbert curve through their centroids (x, y).
 
     The operator tiles the owned cells in runs of 256 consecutive cells of the CALLER's numbering
-    (rdycore_amd/csrc/rdyhip_api.hip), so that numbering decides how many edges are cut by tile
+    (rdycore_amd/csrc/host_layout.h, layout_cut_tiles), so that numbering decides how many edges are cut by tile
     boundaries.  A mesh in generator / row-major / partitioner order is best renumbered once by its
     owner before the operator is created (all of its arrays then move together; DESIGN.md section 7
     has the measurements): `conn = conn[hilbert_cell_order(centroids)]`.

@@ -414,7 +414,7 @@ def test_error_behaviour():
 @pytest.mark.parametrize("kind", ["tri", "quad"])
 def test_random_cell_numbering(kind):
     # a numbering with no locality: every tile's neighbours are almost all outside the tile
-    # (the tiles are then cut small enough for the kernel's fixed halo capacity: rdyhip_api.hip, layout_cut_tiles)
+    # (the tiles are then cut small enough for the kernel's fixed halo capacity: csrc/host_layout.h, layout_cut_tiles)
     rng = np.random.default_rng(3)
     K = 2 * np.pi / 31
     if kind == "tri":

@@ -11,7 +11,7 @@ from rdycore_amd import mesh as M
 from rdycore_amd.operator import RDyFlowConfig, RDyHipError, probe_layout
 
 
-# the capacities every tile is cut to (csrc/swe_kernels.h: TILE_MAX_REC, TILE_MAX_HALO_*; muscl_kernels.h: MUSCL_MAX_RING_*)
+# the capacities every tile is cut to (csrc/tile_format.h: TILE_MAX_REC, TILE_MAX_HALO_*, MUSCL_MAX_RING_*)
 CAP = {3: dict(rec=512, halo=104, ring=256), 4: dict(rec=512, halo=112, ring=168)}
 
 
