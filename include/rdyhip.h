@@ -597,6 +597,65 @@ int rdyhip_output_mean_get(RDyHipOperator op, int32_t var, double *d_mean, doubl
 int rdyhip_output_mean_reset(RDyHipOperator op, int32_t vars, void *stream);
 int rdyhip_output_mean_time(RDyHipOperator op, int32_t var, double *accumulated_time);
 
+/* ---- time series on the device --------------------------------------------------
+ * WriteTimeSeries, the TS monitor of src/time_series.c:530-564, as launches on the caller's stream that append to a log in
+ * device memory; the host reads the log when it writes its file (once per coupling interval, or at the end), so keeping a
+ * series costs the step loop no synchronisation.  Two series, named by `kind` (exactly one per call):
+ *   RDYHIP_SERIES_BOUNDARY_FLUXES  RecordBoundaryFluxes (270-296) + WriteBoundaryFluxes (298-335) +
+ *                                  ResetAccumulatedBoundaryFluxes (508-527).  A record holds one row per boundary edge of the
+ *                                  listed boundaries whose left cell is owned -- boundaries in ascending index, a boundary's
+ *                                  edges in edge_ids order, as the reference's loops -- with (edge length * accumulated
+ *                                  flux) / accumulated time for the 3 components: a product, then a division, the
+ *                                  reference's two roundings (287-289, 325-327).  An accumulated time of exactly 0 divides by
+ *                                  1 (311-313).  A NaN accumulator (an edge dry on both sides) is a NaN in the record.  The
+ *                                  same launch stores +0.0 into the accumulators of EVERY boundary edge, the unlisted
+ *                                  boundaries and the edges behind ghost cells included (520-523).
+ *   RDYHIP_SERIES_OBSERVATIONS     InitObservations (165-250) + WriteObservations (395-448) with the VecCopy at 541: a record
+ *                                  holds the 3 components of the state in every site's cell.
+ *   - rdyhip_series_observations_enable / rdyhip_series_boundary_fluxes_enable (InitTimeSeries, 253-266) allocate the log --
+ *     `capacity` records of entries x 3 doubles, entries = the number of sites S or of recorded edges E -- and upload the
+ *     site / row / edge-length tables; the bytes are counted in RDyHipLayoutInfo.device_bytes and freed by rdyhip_destroy.
+ *     Apart from rdyhip_series_read the only calls here that may synchronise.  A second enable of the same kind:
+ *     RDYHIP_ERR_USER.  Sites are owned-cell indices (each range-checked on the host, mapped to the local cell where the owned
+ *     cells are not numbered first); a site may repeat.  `boundaries`: the indices of the listed boundaries (what the reference
+ *     calls not auto-generated), NULL: every boundary; a boundary named twice counts once.  num_sites == 0, or E == 0 (a rank
+ *     without an owned boundary edge, an empty list), is valid: records then hold nothing and nothing is launched -- so with
+ *     E == 0 the accumulators, which no record of this rank reads, stay as they are -- but the times and counts advance.
+ *   - rdyhip_series_boundary_edges: the recorded edges in record order, their local edge ids and their boundaries (pointers valid
+ *     until rdyhip_destroy): what a host needs for the metadata columns of its file, edge centroid, normal and condition type
+ *     (InitBoundaryFluxes).  rdyhip_series_plan_boundary_edges: the same plan from the mesh arrays alone -- no device, no
+ *     operator; the two output arrays need room for the edges of the listed boundaries and may be NULL (only the count).
+ *   - rdyhip_series_boundary_fluxes_add_time: AccumulateBoundaryFluxes (464-468), accumulated_time += dt.  Host-side only.  The
+ *     accumulation of dt x flux itself happens in the evaluations (the step's own dt), as in the reference's PETSc path (500).
+ *   - rdyhip_series_record enqueues ONE launch on `stream` and appends `time` to a host-side list.  u_local (device,
+ *     [num_cells][3]) is needed only for observations.  For boundary fluxes the call also sets the accumulated time back to 0,
+ *     and it must be ordered after the evaluations whose fluxes it records: launching on their stream does that.  A full log:
+ *     RDYHIP_ERR_USER, nothing is launched and neither the accumulators nor the accumulated time change.  A series that is not
+ *     enabled: RDYHIP_ERR_USER.
+ *   - rdyhip_series_info: rows of a record, records in the log, capacity, and the accumulated time (boundary fluxes; 0 for
+ *     observations); any output may be NULL.
+ *   - rdyhip_series_read copies records [first, first + count) ([count][entries][3]) and their times to the host and synchronises
+ *     `stream` for that: the only blocking call.  rdyhip_series_device_log hands out the device pointer of the whole log
+ *     ([capacity][entries][3]) for a view without a copy; reads of it are the caller's to order.
+ *   - rdyhip_series_clear sets the number of records to 0; the accumulated time of the boundary series is untouched.
+ * Runge-Kutta: every stage evaluation of rdyhip_rk4_step adds its dt x flux to the accumulators, as every RHS evaluation of the
+ * reference's PETSc path does (TSRK calls OperatorRHSFunction four times); a record reports what is there.
+ * Every argument error (null operator, unknown kind, a null array where one is needed, a negative count or capacity, a boundary
+ * index or a site out of range) is RDYHIP_ERR_USER and is reported before any device call. */
+#define RDYHIP_SERIES_OBSERVATIONS 1
+#define RDYHIP_SERIES_BOUNDARY_FLUXES 2
+int rdyhip_series_observations_enable(RDyHipOperator op, int32_t num_sites, const int32_t *owned_cell_ids /* host */, int32_t capacity);
+int rdyhip_series_boundary_fluxes_enable(RDyHipOperator op, int32_t num_listed, const int32_t *boundaries /* host; NULL: all */, int32_t capacity);
+int rdyhip_series_boundary_edges(RDyHipOperator op, int32_t *num_edges, const int32_t **local_edge_ids, const int32_t **boundary_of_edge);
+int rdyhip_series_plan_boundary_edges(const RDyHipMesh *mesh, int32_t num_boundaries, const RDyHipBoundary *boundaries, int32_t num_listed,
+                                      const int32_t *listed, int32_t *num_edges, int32_t *local_edge_ids, int32_t *boundary_of_edge);
+int rdyhip_series_boundary_fluxes_add_time(RDyHipOperator op, double dt);
+int rdyhip_series_record(RDyHipOperator op, int32_t kind, double time, const double *u_local, void *stream);
+int rdyhip_series_info(RDyHipOperator op, int32_t kind, int32_t *entries, int32_t *count, int32_t *capacity, double *accumulated_time);
+int rdyhip_series_read(RDyHipOperator op, int32_t kind, int32_t first, int32_t count, double *times, double *values /* host */, void *stream);
+int rdyhip_series_device_log(RDyHipOperator op, int32_t kind, const double **d_log);
+int rdyhip_series_clear(RDyHipOperator op, int32_t kind);
+
 /* ---- introspection ----------------------------------------------------------
  * numbers describing the device layout, for DESIGN.md / bench.py */
 typedef struct {

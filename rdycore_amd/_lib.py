@@ -105,6 +105,17 @@ SYMBOLS = {
     "rdyhip_output_mean_get": (C.c_int, [_H, C.c_int32, C.c_void_p, c_double_p, C.c_void_p]),
     "rdyhip_output_mean_reset": (C.c_int, [_H, C.c_int32, C.c_void_p]),
     "rdyhip_output_mean_time": (C.c_int, [_H, C.c_int32, c_double_p]),
+    "rdyhip_series_observations_enable": (C.c_int, [_H, C.c_int32, c_int32_p, C.c_int32]),
+    "rdyhip_series_boundary_fluxes_enable": (C.c_int, [_H, C.c_int32, c_int32_p, C.c_int32]),
+    "rdyhip_series_boundary_edges": (C.c_int, [_H, c_int32_p, C.POINTER(c_int32_p), C.POINTER(c_int32_p)]),
+    "rdyhip_series_plan_boundary_edges": (C.c_int, [C.POINTER(RDyHipMesh), C.c_int32, C.POINTER(RDyHipBoundary), C.c_int32, c_int32_p,
+                                                    c_int32_p, c_int32_p, c_int32_p]),
+    "rdyhip_series_boundary_fluxes_add_time": (C.c_int, [_H, C.c_double]),
+    "rdyhip_series_record": (C.c_int, [_H, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]),
+    "rdyhip_series_info": (C.c_int, [_H, C.c_int32, c_int32_p, c_int32_p, c_int32_p, c_double_p]),
+    "rdyhip_series_read": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, c_double_p, c_double_p, C.c_void_p]),
+    "rdyhip_series_device_log": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_void_p)]),
+    "rdyhip_series_clear": (C.c_int, [_H, C.c_int32]),
     "rdyhip_halo_create": (C.c_int, [_H, C.c_void_p, C.c_int32, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p, C.POINTER(C.c_void_p)]),
     "rdyhip_halo_destroy": (C.c_int, [C.POINTER(C.c_void_p)]),
     "rdyhip_halo_overlaps": (C.c_int32, [C.c_void_p]),

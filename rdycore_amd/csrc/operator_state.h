@@ -172,6 +172,21 @@ struct RDyHipOperator_s : LayoutCounts {
   // rdyhip_output_mean_*: one [n_owned][3] accumulator per enabled variable (bit i of RDYHIP_OUTPUT_*) and the time it spans
   DevBuf<double>  d_out_acc[3];
   double          out_time[3] = {0.0, 0.0, 0.0};
+  // rdyhip_series_*: the two device logs of WriteTimeSeries (index 0: observations, 1: boundary fluxes), `capacity` records
+  // of entries x 3 doubles each, and the time of every record on the host
+  struct Series {
+    bool                enabled = false;
+    int32_t             entries = 0, capacity = 0;
+    DevBuf<double>      d_log;
+    std::vector<double> times;   // size() = the number of records
+  } series[2];
+  DevBuf<int32_t>      d_ser_sites, d_ser_slot;   // [S] local cell of every site; [K] row of boundary edge k in a record, or -1
+  DevBuf<double>       d_ser_len;                 // [K] edge lengths
+  double               ser_btime = 0.0;           // boundary_fluxes.accumulated_time
+  std::vector<int32_t> h_ser_edge, h_ser_bnd;     // [E] local edge id and boundary of every recorded edge
+  // what the record plan needs of the boundary edges (series_plan.h), kept at create beside h_bedge / h_boff
+  std::vector<double>  h_blen;     // [K] edges.lengths
+  std::vector<int32_t> h_bghost;   // the boundary edges whose left cell is a ghost
 
   int64_t device_bytes = 0;
 };

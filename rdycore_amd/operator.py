@@ -29,6 +29,7 @@ LIMITER_MINMOD, LIMITER_NONE, LIMITER_VANLEER = 0, 1, 2   # RDyLimiterType, incl
 
 PHASE_ALL, PHASE_INTERIOR, PHASE_HALO = 0, 1, 2
 OUTPUT_SOLUTION, OUTPUT_PRIMITIVE_VARIABLES, OUTPUT_SOURCES = 1, 2, 4   # RDYHIP_OUTPUT_*: the time-averaged output fields
+SERIES_OBSERVATIONS, SERIES_BOUNDARY_FLUXES = 1, 2                      # RDYHIP_SERIES_*: the time series kept on the device
 
 
 @dataclasses.dataclass
@@ -125,6 +126,24 @@ def probe_layout(config: "RDyFlowConfig", mesh: RDyMesh, condition_types: Option
     info = _lib.RDyHipLayoutInfo()
     _lib.check(_lib.load().rdyhip_probe_layout(C.byref(cfg), C.byref(m), nb, barr, C.byref(info)))
     return {k: getattr(info, k) for k, _ in info._fields_}
+
+
+def plan_series_boundary_edges(mesh: RDyMesh, boundaries=None):
+    """rdyhip_series_plan_boundary_edges: which boundary edges a boundary-flux record of `mesh` holds -- (local edge id,
+    boundary) per row, in record order -- for the listed boundaries (None: all).  Host only, no device needed."""
+    cfg, m, nb, barr, _, _keep = _abi_arguments(RDyFlowConfig(), mesh, None)
+    room = max(sum(b.num_edges for b in mesh.boundaries), 1)
+    e, b = np.zeros(room, dtype=np.int32), np.zeros(room, dtype=np.int32)
+    n = C.c_int32()
+    if boundaries is None:
+        nl, lp = 0, None
+    else:
+        listed = np.ascontiguousarray(boundaries, dtype=np.int32).ravel()
+        arg = listed if listed.size else np.zeros(1, dtype=np.int32)
+        nl, lp = int(listed.size), arg.ctypes.data_as(_lib.c_int32_p)
+    _lib.check(_lib.load().rdyhip_series_plan_boundary_edges(C.byref(m), nb, barr, nl, lp, C.byref(n), e.ctypes.data_as(_lib.c_int32_p),
+                                                            b.ctypes.data_as(_lib.c_int32_p)))
+    return e[:n.value].copy(), b[:n.value].copy()
 
 
 class Operator:
@@ -261,6 +280,80 @@ class Operator:
         t = C.c_double()
         _lib.check(_lib.load().rdyhip_output_mean_time(self._h, int(var), C.byref(t)))
         return t.value
+
+    # -- time series on the device (WriteTimeSeries, src/time_series.c:530-564) -----------------------------------------------
+    def enable_observation_series(self, owned_cell_ids, capacity: int):
+        """rdyhip_series_observations_enable (InitObservations): a device log of `capacity` records of the state in the cells
+        `owned_cell_ids` (owned-cell indices; a site may repeat)"""
+        ids = np.ascontiguousarray(owned_cell_ids, dtype=np.int32).ravel()
+        arg = ids if ids.size else np.zeros(1, dtype=np.int32)
+        _lib.check(_lib.load().rdyhip_series_observations_enable(self._h, int(ids.size), arg.ctypes.data_as(_lib.c_int32_p), int(capacity)))
+
+    def enable_boundary_flux_series(self, capacity: int, boundaries=None):
+        """rdyhip_series_boundary_fluxes_enable (InitBoundaryFluxes): a device log of `capacity` records with one row per boundary
+        edge of `boundaries` (indices; None: all) whose left cell is owned"""
+        if boundaries is None:
+            _lib.check(_lib.load().rdyhip_series_boundary_fluxes_enable(self._h, 0, None, int(capacity)))
+            return
+        b = np.ascontiguousarray(boundaries, dtype=np.int32).ravel()
+        arg = b if b.size else np.zeros(1, dtype=np.int32)      # an empty list is a list, not "all"
+        _lib.check(_lib.load().rdyhip_series_boundary_fluxes_enable(self._h, int(b.size), arg.ctypes.data_as(_lib.c_int32_p), int(capacity)))
+
+    def series_boundary_edges(self):
+        """rdyhip_series_boundary_edges: (local edge id, boundary) of every row of a boundary-flux record, in record order"""
+        n = C.c_int32()
+        e, b = _lib.c_int32_p(), _lib.c_int32_p()
+        _lib.check(_lib.load().rdyhip_series_boundary_edges(self._h, C.byref(n), C.byref(e), C.byref(b)))
+        if n.value == 0:
+            return np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32)
+        return np.ctypeslib.as_array(e, (n.value,)).copy(), np.ctypeslib.as_array(b, (n.value,)).copy()
+
+    def series_add_time(self, dt: float):
+        """AccumulateBoundaryFluxes (rdyhip_series_boundary_fluxes_add_time): accumulated_time += dt"""
+        _lib.check(_lib.load().rdyhip_series_boundary_fluxes_add_time(self._h, float(dt)))
+
+    def series_record(self, kind: int, time: float, u_local: Optional[torch.Tensor] = None):
+        """rdyhip_series_record: one record of SERIES_OBSERVATIONS (the state `u_local`, [num_cells,3]) or SERIES_BOUNDARY_FLUXES
+        appended to its device log, one launch on the current stream"""
+        if u_local is not None:
+            n = self.mesh.num_cells
+            if not (isinstance(u_local, torch.Tensor) and u_local.is_cuda and u_local.dtype == torch.float64 and u_local.is_contiguous()
+                    and u_local.numel() == 3 * n):
+                raise RDyHipError(83, f"u_local must be a contiguous float64 device tensor of {n} cells x 3")
+        _lib.check(_lib.load().rdyhip_series_record(self._h, int(kind), float(time), _ptr(u_local) if u_local is not None else None, _stream()))
+
+    def series_info(self, kind: int) -> dict:
+        """rdyhip_series_info: rows of a record, records in the log, capacity, accumulated time"""
+        e, n, cap, t = C.c_int32(), C.c_int32(), C.c_int32(), C.c_double()
+        _lib.check(_lib.load().rdyhip_series_info(self._h, int(kind), C.byref(e), C.byref(n), C.byref(cap), C.byref(t)))
+        return {"entries": e.value, "count": n.value, "capacity": cap.value, "accumulated_time": t.value}
+
+    def series_read(self, kind: int, first: int = 0, count: Optional[int] = None):
+        """rdyhip_series_read: (times [count], values [count, entries, 3]) of records [first, first + count) as numpy arrays
+        (count=None: all from `first`); synchronises the current stream"""
+        info = self.series_info(kind)
+        if count is None:
+            count = max(info["count"] - int(first), 0)
+        times = np.zeros(max(int(count), 0))
+        values = np.zeros((max(int(count), 0), info["entries"], 3))
+        tp = times.ctypes.data_as(_lib.c_double_p) if times.size else None
+        vp = values.ctypes.data_as(_lib.c_double_p) if values.size else None
+        _lib.check(_lib.load().rdyhip_series_read(self._h, int(kind), int(first), int(count), tp, vp, _stream()))
+        return times, values
+
+    def series_device_log(self, kind: int) -> torch.Tensor:
+        """rdyhip_series_device_log: the whole log as a [capacity, entries, 3] device tensor, no copy"""
+        p = C.c_void_p()
+        _lib.check(_lib.load().rdyhip_series_device_log(self._h, int(kind), C.byref(p)))
+        info = self.series_info(kind)
+        shape = (info["capacity"], info["entries"], 3)
+        if shape[0] * shape[1] == 0:
+            return torch.zeros(shape, dtype=torch.float64, device="cuda")
+        return torch.as_tensor(_DeviceArray(p.value, (shape[0] * shape[1] * 3,), self), device="cuda").view(shape)
+
+    def series_clear(self, kind: int):
+        """rdyhip_series_clear: the log holds no records; the accumulated time of the boundary series stays"""
+        _lib.check(_lib.load().rdyhip_series_clear(self._h, int(kind)))
 
     # -- second order: ComputeLeastSquaresGradients for the owned cells (src/operator_fluxes_ceed.c:998-1042)
     def compute_gradients(self, u_local: torch.Tensor, phase: int = PHASE_ALL):

@@ -17,6 +17,10 @@ evaluations, with the state kept on the GPU.
   * time-averaged output (`means`: a mask of the operator's OUTPUT_* bits): what the TS monitor does around TSSolve for
     WriteXDMFOutput's OutputVars (src/xdmf_output.c:436-504) -- one accumulate of dt x (solution, primitive variables,
     sources) for the initial state and one after every step, on the device (rdyhip_output_mean_accumulate).
+  * time series (`series`: a TimeSeries): what the TS monitor WriteTimeSeries does (src/time_series.c:530-564) -- the state
+    at a list of observation sites every `observation_interval` steps, the accumulated boundary fluxes every
+    `boundary_flux_interval` steps -- appended to logs that stay on the device (rdyhip_series_record); nothing is read back
+    until the caller asks for the log.
   * RDyAdvance (src/rdyadvance.c:261-383): advance to the next coupling time
     with the last step shortened to land on it (TS_EXACTFINALTIME_MATCHSTEP),
     and, when adaptive time stepping is on, rescale dt from the previous
@@ -25,7 +29,7 @@ evaluations, with the state kept on the GPU.
 from __future__ import annotations
 
 import dataclasses
-from typing import Optional
+from typing import Optional, Sequence
 
 import torch
 import torch.distributed as dist
@@ -65,12 +69,36 @@ class AdaptiveTime:
     max_increase_factor: float = 2.0
 
 
+@dataclasses.dataclass
+class TimeSeries:
+    """output.time_series of the reference's configuration (observations.sites / observations.interval, boundary_fluxes) for
+    EulerStepper(series=...).  `observation_sites`: owned-cell indices; an interval of 0 turns its series off;
+    `boundaries`: the boundaries whose fluxes are recorded (None: all -- the reference leaves out the auto-generated ones);
+    `capacity`: records each device log has room for (read the log and clear it before it is full)."""
+    observation_sites: Sequence[int] = ()
+    observation_interval: int = 0
+    boundary_flux_interval: int = 0
+    boundaries: Optional[Sequence[int]] = None
+    capacity: int = 1024
+
+
 class EulerStepper:
     """the explicit TS of RDyAdvance: forward Euler (default) or, with temporal="rk4", classical Runge-Kutta"""
 
     def __init__(self, op, halo=None, adaptive: Optional[AdaptiveTime] = None, fused: bool = True, forcing=None, temporal: str = "euler",
-                 means: int = 0):
-        """`means`: which time-averaged output fields to keep (OUTPUT_SOLUTION | OUTPUT_PRIMITIVE_VARIABLES | OUTPUT_SOURCES of
+                 means: int = 0, series: Optional[TimeSeries] = None):
+        """`series`: a TimeSeries, or None (the default): none of the operator's series calls is made.  With one, the stepper
+        plays WriteTimeSeries (src/time_series.c:530-564): one monitor call before the first step of its life (step 0) and one
+        after every step, each doing, in this order,
+          1. observations: if observation_interval is nonzero and step % observation_interval == 0, a record of the current
+             state (after a fused Euler step: the step's output array).  The reference never advances observations.last_step,
+             so there is no guard against a repeated step here either;
+          2. if the boundary series is on, add_time(dt) with the INTERVAL's dt (rdy->dt, src/time_series.c:467), also after a
+             last step that was shortened -- while the kernels accumulate dt x flux with the step's own h: the reference's
+             arithmetic, kept;
+          3. if step % boundary_flux_interval == 0 and step > last_step: a boundary-flux record, and last_step = step.
+        The record times are the stepper's `time`.  series_read() returns a log.
+        `means`: which time-averaged output fields to keep (OUTPUT_SOLUTION | OUTPUT_PRIMITIVE_VARIABLES | OUTPUT_SOURCES of
         rdycore_amd.operator; 0: none, and none of the operator's output-mean calls is made).  With bits set the stepper
         accumulates once before the first step of its life -- the initial state, whatever the primitive variables and the
         sources hold then -- and once after every step.  Every accumulate is weighted with the INTERVAL's dt, also after a
@@ -99,6 +127,32 @@ class EulerStepper:
         self.means = int(means)
         if self.means:
             op.enable_output_means(self.means)
+        self.series = series
+        self._series_last_step = -1   # boundary_fluxes.last_step (InitBoundaryFluxes)
+        if series is not None:
+            if series.observation_interval:
+                op.enable_observation_series(series.observation_sites, series.capacity)
+            if series.boundary_flux_interval:
+                op.enable_boundary_flux_series(series.capacity, series.boundaries)
+
+    def _series_monitor(self, dt, state):
+        """WriteTimeSeries(ts, step, time, X) for the step count and time the stepper stands at"""
+        from .operator import SERIES_BOUNDARY_FLUXES, SERIES_OBSERVATIONS
+        s = self.series
+        if s.observation_interval and self.step % s.observation_interval == 0:
+            self.op.series_record(SERIES_OBSERVATIONS, self.time, state)
+        if s.boundary_flux_interval:
+            self.op.series_add_time(dt)
+            if self.step % s.boundary_flux_interval == 0 and self.step > self._series_last_step:
+                self.op.series_record(SERIES_BOUNDARY_FLUXES, self.time)
+                self._series_last_step = self.step
+
+    def series_read(self, kind: int, clear: bool = False):
+        """the log of one series, (times, values [records, entries, 3]); `clear`: the log then starts empty"""
+        out = self.op.series_read(kind)
+        if clear:
+            self.op.series_clear(kind)
+        return out
 
     def output_mean(self, var: int):
         """ComputeMean + ResetOutputVar (src/xdmf_output.c:211-241) of one variable: (mean [owned,3], accumulated time); the
@@ -140,6 +194,8 @@ class EulerStepper:
         m = self.means
         if m and self.step == 0:
             self.op.accumulate_output_means(m, dt, u_local)      # the monitor's call at step 0
+        if self.series is not None and self.step == 0:
+            self._series_monitor(dt, u_local)
         while self.time < t_end * (1.0 - 1e-14):
             h = min(dt, t_end - self.time)       # TS_EXACTFINALTIME_MATCHSTEP
             if self.temporal == "rk4":
@@ -165,6 +221,8 @@ class EulerStepper:
                     self.op.accumulate_output_means(1, dt, u_local)
             self.time += h
             self.step += 1
+            if self.series is not None:
+                self._series_monitor(dt, cur if self.temporal == "euler" and self.fused else u_local)
         if cur is not u_local:
             u_local.copy_(cur)                   # an odd number of steps ended in the second buffer (euler, fused)
         if a is not None:
