@@ -656,6 +656,69 @@ int rdyhip_series_read(RDyHipOperator op, int32_t kind, int32_t first, int32_t c
 int rdyhip_series_device_log(RDyHipOperator op, int32_t kind, const double **d_log);
 int rdyhip_series_clear(RDyHipOperator op, int32_t kind);
 
+/* ---- state read-out: owned-cell getters and error sums -----------------------------
+ * RDyGetOwnedCellHeights / XMomenta / YMomenta (src/rdydata.c:171-205) and the rank-local loops of RDyMMSComputeErrorNorms
+ * (src/rdymms.c:869-880) without the blocking copy of the whole [num_cells][3] state that VecGetArrayRead makes of a Vec placed
+ * on a device array: a de-interleave launch picks the wanted components on the device, 8 bytes per cell and component cross to
+ * the host on the operator's copy stream, and only the call that hands the values over waits -- for that copy alone, not for
+ * the device.  `comps` is a mask of RDYHIP_COMPONENT_*; `comp` is exactly one of them.
+ *   - rdyhip_state_planes, the device form: ONE launch on `stream`, nothing else.
+ *       d_planes[k][o] = u_local[loc(o)][c_k]      k over the set bits c_k of `comps`, ascending; o over the owned cells
+ *     d_planes is device memory, [popcount(comps)][num_owned_cells]; u_local is [num_cells][3]; loc(o) is the local cell of owned
+ *     cell o (o itself where the owned cells are numbered first).  Values are copied, never computed: every bit pattern
+ *     survives (-0.0, NaN payloads, denormals).
+ *   - rdyhip_state_read_begin, the host form: the same launch on `stream` into planes the operator owns, an event, a
+ *     device-to-host copy into pinned memory the operator owns on the operator's copy stream behind that event (the stream of
+ *     the rdyhip_set_*_on setters), and a second event.  It returns without blocking; nothing waits on the host and `stream`
+ *     does not wait for the copy.  u_local is read at the call's place in `stream`: work enqueued later on that stream may
+ *     overwrite it, rdyhip_rk4_step (which rewrites it in place) included.  The buffers are allocated by the first call that
+ *     needs them and grow only (a wider mask later grows them); that one call may synchronise.  The device planes are counted
+ *     in RDyHipLayoutInfo.device_bytes; rdyhip_destroy frees everything after waiting for a copy still in flight.
+ *     A begin while an earlier read has not landed (not waited for): the new launch is ordered behind the earlier copy, so the
+ *     device planes are never overwritten under a running copy, and the earlier result is discarded.  This is not an error.
+ *   - rdyhip_state_read_ready: *ready = 1 once the copy has finished (an event query; it does not stand in for _wait).
+ *   - rdyhip_state_read_wait blocks until the copy of the last begin has finished -- on its event only.  The only blocking call.
+ *   - rdyhip_state_read_get copies one plane from pinned memory to `values` (host, [size]).  size != num_owned_cells:
+ *     RDYHIP_ERR_ARG_SIZ (CheckNumOwnedCells, src/rdydata.c:54-58).  A component the last begin did not ask for, no begin at all,
+ *     or a read that has not been waited for: RDYHIP_ERR_USER.  It never blocks.
+ *   - rdyhip_state_read_ptr hands out the pinned plane itself (NULL on a rank that owns nothing), valid until the next begin.
+ *   A rank that owns nothing: nothing is launched or copied; _wait and _get (size == 0) succeed.
+ *
+ * rdyhip_error_sums: for e = u_local[loc(o)][c] - d_exact[o][c] (one subtraction, as the VecAYPX at src/rdymms.c:857; d_exact is
+ * device memory, [num_owned_cells][3], NULL = zeros) over the owned cells o of THIS rank,
+ *     l1[c] += |e| * area(o)     l2_squared[c] += e * e * area(o)     linf[c] = max(|e|, linf[c])     area += area(o)
+ * The MPI_Allreduce over the ranks and the square root of the L2 sums (src/rdymms.c:885-891) stay with the caller.  With
+ * d_exact == NULL and h >= 0, l1[0] is the water volume of the rank.  Two launches on `stream` -- RDYHIP_ERROR_SUMS_BLOCK lanes
+ * per workgroup, min(ceil(num_owned_cells / RDYHIP_ERROR_SUMS_BLOCK), RDYHIP_ERROR_SUMS_MAX_WORKGROUPS) workgroups that each
+ * write one partial record of 10 doubles, then one workgroup that sums the records in a fixed order -- and an 80-byte copy into
+ * pinned memory behind an event; the call does not block.  No floating-point atomics: the result is the same bits from run to
+ * run and from stream to stream.  The sums are fused multiply-adds (|e| * area and (e * e) * area enter unrounded).  A NaN in e
+ * makes l1 and l2_squared of its component NaN; linf with a NaN input is unspecified (the reference's PetscMax is
+ * order-dependent there).  The cell areas [num_owned_cells] and the records [workgroups + 1][10] (the last one is the result) go
+ * to the device at the first call, which may synchronise, and are counted in RDyHipLayoutInfo.device_bytes.  A call while an
+ * earlier one is still running is ordered behind it and replaces its result.  A rank that owns nothing: all zeros, nothing
+ * is launched.
+ *   - rdyhip_error_sums_get waits for the result of the last call (its event only) and copies it out: the only blocking call.
+ *     No call before it: RDYHIP_ERR_USER.
+ * Every argument error (a null operator, a null array where one is needed, `comps` outside 1..7, a `comp` that is not one bit)
+ * is RDYHIP_ERR_USER and is reported before any device call. */
+#define RDYHIP_COMPONENT_H 1
+#define RDYHIP_COMPONENT_HU 2
+#define RDYHIP_COMPONENT_HV 4
+#define RDYHIP_ERROR_SUMS_BLOCK 256
+#define RDYHIP_ERROR_SUMS_MAX_WORKGROUPS 1024
+typedef struct {
+  double l1[3], l2_squared[3], linf[3], area;
+} RDyHipErrorSums;
+int rdyhip_state_planes(RDyHipOperator op, int32_t comps, const double *u_local, double *d_planes, void *stream);
+int rdyhip_state_read_begin(RDyHipOperator op, int32_t comps, const double *u_local, void *stream);
+int rdyhip_state_read_ready(RDyHipOperator op, int32_t *ready);
+int rdyhip_state_read_wait(RDyHipOperator op);
+int rdyhip_state_read_get(RDyHipOperator op, int32_t comp, int32_t size, double *values /* host */);
+int rdyhip_state_read_ptr(RDyHipOperator op, int32_t comp, const double **pinned_values);
+int rdyhip_error_sums(RDyHipOperator op, const double *u_local, const double *d_exact, void *stream);
+int rdyhip_error_sums_get(RDyHipOperator op, RDyHipErrorSums *out);
+
 /* ---- introspection ----------------------------------------------------------
  * numbers describing the device layout, for DESIGN.md / bench.py */
 typedef struct {

@@ -57,6 +57,10 @@ class RDyHipHaloFormInfo(C.Structure):
     _fields_ = [("form", C.c_int32), ("source", C.c_int32), ("trial_steps", C.c_int32), ("in_order_ms", C.c_double), ("two_stream_ms", C.c_double)]
 
 
+class RDyHipErrorSums(C.Structure):
+    _fields_ = [("l1", C.c_double * 3), ("l2_squared", C.c_double * 3), ("linf", C.c_double * 3), ("area", C.c_double)]
+
+
 # every symbol include/rdyhip.h declares: name -> (restype, argtypes)
 _H = C.c_void_p  # RDyHipOperator
 SYMBOLS = {
@@ -116,6 +120,14 @@ SYMBOLS = {
     "rdyhip_series_read": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, c_double_p, c_double_p, C.c_void_p]),
     "rdyhip_series_device_log": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_void_p)]),
     "rdyhip_series_clear": (C.c_int, [_H, C.c_int32]),
+    "rdyhip_state_planes": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rdyhip_state_read_begin": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p]),
+    "rdyhip_state_read_ready": (C.c_int, [_H, c_int32_p]),
+    "rdyhip_state_read_wait": (C.c_int, [_H]),
+    "rdyhip_state_read_get": (C.c_int, [_H, C.c_int32, C.c_int32, c_double_p]),
+    "rdyhip_state_read_ptr": (C.c_int, [_H, C.c_int32, C.POINTER(c_double_p)]),
+    "rdyhip_error_sums": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rdyhip_error_sums_get": (C.c_int, [_H, C.POINTER(RDyHipErrorSums)]),
     "rdyhip_halo_create": (C.c_int, [_H, C.c_void_p, C.c_int32, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p, C.POINTER(C.c_void_p)]),
     "rdyhip_halo_destroy": (C.c_int, [C.POINTER(C.c_void_p)]),
     "rdyhip_halo_overlaps": (C.c_int32, [C.c_void_p]),

@@ -101,6 +101,36 @@ struct StageRing {
   }
 };
 
+// The read-out of the state (rdyhip_state_read_*, rdyhip_error_sums; readout_kernels.h): device planes and pinned host planes
+// of the getters, the areas / partial records / pinned result of the error sums, and the events the host waits on.  Everything
+// is allocated by the first call that needs it and grows only.
+struct Readout {
+  enum State { NONE, IN_FLIGHT, LANDED };
+  // the getters
+  DevBuf<double> d_planes;            // [popcount(comps)][n_owned], room for the widest mask asked for so far
+  double        *h_planes = nullptr;  // pinned, as many doubles as d_planes
+  size_t         h_cap = 0;
+  hipEvent_t     launched = nullptr, done = nullptr;   // the de-interleave launch on the caller's stream; the copy on StageRing::copy
+  State          state = NONE;
+  int32_t        comps = 0;           // the mask of the last begin
+  // the error sums
+  DevBuf<double> d_area, d_records;   // [n_owned]; [err_wg + 1][10]: the workgroups' records, then the result
+  double        *h_sums = nullptr;    // pinned, 10 doubles (RDyHipErrorSums)
+  hipEvent_t     sums_done = nullptr;
+  State          sums_state = NONE;
+  int            err_wg = 0;
+  Readout() = default;
+  Readout(const Readout &) = delete;
+  Readout &operator=(const Readout &) = delete;
+  ~Readout() {
+    if (h_planes) (void)hipHostFree(h_planes);
+    if (h_sums) (void)hipHostFree(h_sums);
+    if (launched) (void)hipEventDestroy(launched);
+    if (done) (void)hipEventDestroy(done);
+    if (sums_done) (void)hipEventDestroy(sums_done);
+  }
+};
+
 struct RDyHipHalo_s;
 // (the layout's numbers -- n_cells, n_owned, S, K, n_halo, ntiles, ... -- are the base class's, copied from HostLayout::counts)
 struct RDyHipOperator_s : LayoutCounts {
@@ -187,6 +217,8 @@ struct RDyHipOperator_s : LayoutCounts {
   // what the record plan needs of the boundary edges (series_plan.h), kept at create beside h_bedge / h_boff
   std::vector<double>  h_blen;     // [K] edges.lengths
   std::vector<int32_t> h_bghost;   // the boundary edges whose left cell is a ghost
+  // rdyhip_state_read_* / rdyhip_error_sums (declared after `stage`: its copy stream outlives these buffers)
+  Readout readout;
 
   int64_t device_bytes = 0;
 };

@@ -30,6 +30,7 @@ LIMITER_MINMOD, LIMITER_NONE, LIMITER_VANLEER = 0, 1, 2   # RDyLimiterType, incl
 PHASE_ALL, PHASE_INTERIOR, PHASE_HALO = 0, 1, 2
 OUTPUT_SOLUTION, OUTPUT_PRIMITIVE_VARIABLES, OUTPUT_SOURCES = 1, 2, 4   # RDYHIP_OUTPUT_*: the time-averaged output fields
 SERIES_OBSERVATIONS, SERIES_BOUNDARY_FLUXES = 1, 2                      # RDYHIP_SERIES_*: the time series kept on the device
+COMPONENT_H, COMPONENT_HU, COMPONENT_HV = 1, 2, 4                       # RDYHIP_COMPONENT_*: the planes of the state read-out
 
 
 @dataclasses.dataclass
@@ -354,6 +355,61 @@ class Operator:
     def series_clear(self, kind: int):
         """rdyhip_series_clear: the log holds no records; the accumulated time of the boundary series stays"""
         _lib.check(_lib.load().rdyhip_series_clear(self._h, int(kind)))
+
+    # -- state read-out: RDyGetOwnedCell{Heights,XMomenta,YMomenta} (src/rdydata.c:171-205), RDyMMSComputeErrorNorms (src/rdymms.c:850-903)
+    def _check_state(self, u_local, name="u_local", cells=None):
+        n = self.mesh.num_cells if cells is None else cells
+        if not (isinstance(u_local, torch.Tensor) and u_local.is_cuda and u_local.dtype == torch.float64 and u_local.is_contiguous()
+                and u_local.numel() == 3 * n):
+            raise RDyHipError(83, f"{name} must be a contiguous float64 device tensor of {n} cells x 3")
+
+    def state_planes(self, u_local: torch.Tensor, comps: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """rdyhip_state_planes: [popcount(comps), owned] device tensor, plane k = the k-th component of COMPONENT_H | COMPONENT_HU |
+        COMPONENT_HV in `comps` (ascending) of the owned cells, bit for bit; one launch on the current stream.  `out`: a
+        contiguous float64 device tensor with room for the planes, written from its start."""
+        self._check_state(u_local)
+        k = bin(int(comps) & 7).count("1") if 1 <= int(comps) <= 7 else 0
+        no = self.mesh.num_owned_cells
+        if out is None:
+            out = torch.empty((k, no), dtype=torch.float64, device="cuda")
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() >= k * no):
+            raise RDyHipError(83, f"out must be a contiguous float64 device tensor of at least {k} x {no} values")
+        _lib.check(_lib.load().rdyhip_state_planes(self._h, int(comps), _ptr(u_local), _ptr(out), _stream()))
+        return out
+
+    def read_state_begin(self, u_local: torch.Tensor, comps: int):
+        """rdyhip_state_read_begin: de-interleave `comps` of the owned cells on the current stream and start their copy to pinned
+        host memory on the operator's copy stream; returns at once.  u_local is read at this place in the stream."""
+        self._check_state(u_local)
+        _lib.check(_lib.load().rdyhip_state_read_begin(self._h, int(comps), _ptr(u_local), _stream()))
+
+    def read_state_ready(self) -> bool:
+        """rdyhip_state_read_ready: the copy of the last read_state_begin has finished (an event query)"""
+        out = C.c_int32()
+        _lib.check(_lib.load().rdyhip_state_read_ready(self._h, C.byref(out)))
+        return bool(out.value)
+
+    def read_state(self, comp: int) -> np.ndarray:
+        """rdyhip_state_read_wait + rdyhip_state_read_get: waits for the copy of the last read_state_begin (for that alone) and
+        returns component `comp` (exactly one COMPONENT_*) of the owned cells as a numpy array"""
+        lib = _lib.load()
+        _lib.check(lib.rdyhip_state_read_wait(self._h))
+        out = np.empty(self.mesh.num_owned_cells)
+        _lib.check(lib.rdyhip_state_read_get(self._h, int(comp), int(out.size), out.ctypes.data_as(_lib.c_double_p) if out.size else None))
+        return out
+
+    def error_sums(self, u_local: torch.Tensor, exact: Optional[torch.Tensor] = None) -> dict:
+        """rdyhip_error_sums + rdyhip_error_sums_get: {"l1", "l2_squared", "linf": [3] arrays, "area": float} of u_local - exact over
+        the owned cells of this rank (`exact`: [owned,3] device tensor; None: zeros, so l1[0] is the water volume); the reduction
+        over ranks and the square root of RDyMMSComputeErrorNorms are the caller's"""
+        self._check_state(u_local)
+        if exact is not None:
+            self._check_state(exact, "exact", self.mesh.num_owned_cells)
+        lib = _lib.load()
+        _lib.check(lib.rdyhip_error_sums(self._h, _ptr(u_local), _ptr(exact) if exact is not None else None, _stream()))
+        s = _lib.RDyHipErrorSums()
+        _lib.check(lib.rdyhip_error_sums_get(self._h, C.byref(s)))
+        return {"l1": np.array(s.l1[:]), "l2_squared": np.array(s.l2_squared[:]), "linf": np.array(s.linf[:]), "area": float(s.area)}
 
     # -- second order: ComputeLeastSquaresGradients for the owned cells (src/operator_fluxes_ceed.c:998-1042)
     def compute_gradients(self, u_local: torch.Tensor, phase: int = PHASE_ALL):
