@@ -146,6 +146,10 @@ struct RDyHipOperator_s : LayoutCounts {
   int          interior_shrink = 32;            // the INTERIOR phase leaves 1/interior_shrink of the workgroup slots free (0: none)
   bool         balance_rounds = false;          // size the persistent grid so that all workgroups walk the same number of tiles
   bool         keep_fdiv = false;
+  // RDYHIP_TILE_WALK: PHASE_ALL launches of the first-order / HR tiled kernels over XCD chunks let their workgroups draw
+  // tiles from per-XCD counters (d_tile_draw: 8 draw counters + the exit counter, a cache line apart, zero between launches) instead of a fixed share
+  int             tile_walk = -1;   // -1: by size (launch_rhs), 0 / 1: RDYHIP_TILE_WALK=static / dynamic
+  DevBuf<int32_t> d_tile_draw;
 
   DevBuf<int32_t> d_o2l, d_nbr, d_pos, d_halo_list, d_btype, d_bleft, d_bghost_list;
   DevBuf<double>  d_cn, d_sn, d_coef, d_dzdx, d_dzdy, d_mannings, d_extsrc;

@@ -267,6 +267,16 @@ int launch_rhs(RDyHipOperator op, int32_t phase, int32_t overwrite, int reset_di
         a.extsrc  = op->d_src_water.p;
         a.src_mom = 0;
       }
+      // The dynamic walk: whole-mesh launches over XCD chunks.  INTERIOR launches skip tiles (their draws would run in
+      // series) and HALO launches walk a list: both keep the static walk, and neither touches the counters, so they may
+      // run beside each other as before.  PHASE_ALL launches of one operator already follow each other (the Courant buckets).
+      // Default: from TILE_WALK_MIN_ROUNDS tiles per workgroup.  Measured at 38 (10 M triangles: 6.5 % faster) and at 3.8
+      // (1 M: 13 % slower, three of the four tiles are the static ones anyway); not swept between (RESULTS_LOG section 21).
+      const bool dyn_ok   = tiled_has_dynamic_walk(op->S, xq ? 1 : 0, op->hr, euler_fused) && phase == RDYHIP_PHASE_ALL && a.xcd_chunks > 0 && !a.list;
+      const bool dyn_want = op->tile_walk >= 0 ? op->tile_walk == 1 : (int64_t)a.xcd_chunks * 8 >= (int64_t)TILE_WALK_MIN_ROUNDS * grid;
+      a.tile_walk = dyn_ok && dyn_want ? TILE_WALK_DYNAMIC
+                    : a.phase == RDYHIP_PHASE_INTERIOR                                                ? TILE_WALK_STATIC_SKIP
+                                                                                                       : TILE_WALK_STATIC;
       hipLaunchKernelGGL(HIP_KERNEL_NAME(kfn), dim3(grid), dim3(TILE), op->lds_bytes, st, a, dt, u, f);
     }
   } else {
@@ -374,7 +384,11 @@ int rdyhip_create(const RDyHipConfig *config, const RDyHipMesh *mesh, int32_t nu
     if (const char *e4 = getenv("RDYHIP_PGRID")) {  // measurement knob: the persistent grid itself
       if (atoi(e4) >= 8) op->pgrid = op->pgrid_muscl = atoi(e4) & ~7;
     }
-    if (const char *e5 = getenv("RDYHIP_BALANCE_ROUNDS")) op->balance_rounds = atoi(e5) != 0;
+    if (const char *e5 = getenv("RDYHIP_BALANCE_ROUNDS")) op->balance_rounds = atoi(e5) != 0;  // moot under the dynamic walk
+    if (const char *e6 = getenv("RDYHIP_TILE_WALK")) {
+      if (strcmp(e6, "static") != 0 && strcmp(e6, "dynamic") != 0) return fail(RDYHIP_ERR_USER, "RDYHIP_TILE_WALK is 'static' or 'dynamic', not '%s'", e6);
+      op->tile_walk = strcmp(e6, "dynamic") == 0 ? 1 : 0;
+    }
   }
   const int    maxgrid = std::max(std::max(std::max(op->grid, op->pgrid), op->pgrid_muscl), 1);
   const size_t no = (size_t)op->n_owned, nc = (size_t)op->n_cells, K = (size_t)op->K;
@@ -426,6 +440,7 @@ int rdyhip_create(const RDyHipConfig *config, const RDyHipMesh *mesh, int32_t nu
   if (!rc) rc = op->d_blk_max.zeros((size_t)2 * maxgrid);  // two halves: see launch_rhs(bucket_half)
   if (!rc) rc = op->d_blk_pos.zeros((size_t)2 * maxgrid);
   if (!rc) rc = op->d_courant.zeros(1);
+  if (!rc) rc = op->d_tile_draw.zeros(9 * TILE_DRAW_STRIDE);
   if (!rc) {
     ColdArgs c{};
     c.nbr = op->d_nbr.p; c.cn = op->d_cn.p; c.sn = op->d_sn.p; c.pos = op->d_pos.p; c.e_pos = op->d_e_pos.p;
@@ -434,6 +449,7 @@ int rdyhip_create(const RDyHipConfig *config, const RDyHipMesh *mesh, int32_t nu
     c.n_xedges = op->n_xedges; c.x_rec0 = (int32_t)L.e_lr.size(); c.x_lr = op->d_x_lr.p; c.x_flags = op->d_x_flags.p; c.x_cs = op->d_x_cs.p;
     c.x_cfac = op->d_x_cfac.p; c.x_mid = op->d_x_mid.p;
     c.blk_max = op->d_blk_max.p; c.blk_pos = op->d_blk_pos.p;
+    c.tile_draw = op->d_tile_draw.p;
     rc = op->d_cold.upload(std::vector<ColdArgs>(1, c));
   }
   if (rc) return rc;

@@ -90,8 +90,17 @@ struct ColdArgs {
   const int32_t *gsend_off;   // [n_halo + 1] first send row of the cell at each position of the halo cell list
   const int32_t *gsend_rows;  // rows of the send buffer ([send cells][6])
   double        *gsend_buf;
+  // The dynamic tile walk of the first-order / HR tiled kernels (KernelArgs::tile_walk): counters 0-7 count the tiles drawn
+  // from each XCD's range beyond the workgroups' static ones, counter 8 the workgroups that have left.  Zero between launches:
+  // the workgroup that leaves last zeroes all nine, and the next launch that uses them is ordered behind it on the stream.
+  // One counter per TILE_DRAW_STRIDE words: side by side in one cache line the eight XCDs' draws queue for that line like
+  // draws from ONE counter (measured: the launch took 1.9 x as long, profiles/RESULTS_LOG.md section 21).
+  int32_t       *tile_draw;  // [9 * TILE_DRAW_STRIDE]
 };
+constexpr int TILE_DRAW_STRIDE = 64;  // 256 B
+constexpr int TILE_WALK_MIN_ROUNDS = 32;  // tiles per workgroup from which a launch walks dynamically by default (launch_rhs)
 
+enum { TILE_WALK_STATIC = 0, TILE_WALK_DYNAMIC = 1, TILE_WALK_STATIC_SKIP = 2 };
 struct KernelArgs {
   int32_t        n_owned;    // owned cells
   int32_t        n_work;     // cell kernel: threads with work; tiled kernel: number of tiles to run
@@ -109,6 +118,10 @@ struct KernelArgs {
   int32_t        bucket_off; // first Courant bucket of this launch (launch_rhs(bucket_half))
   int32_t        n_buckets;
   int32_t        reset_diag; // 1: this launch starts a new diagnostic (ResetOperatorDiagnostics): buckets are overwritten
+  int32_t        tile_walk;  // first-order / HR tiled kernel, TILE_WALK_*: DYNAMIC: after its first tile a workgroup draws its
+                             // tiles from its XCD's counter (ColdArgs::tile_draw), set by launch_rhs for PHASE_ALL launches with
+                             // xcd_chunks > 0 only; STATIC_SKIP: the static walk of an INTERIOR phase, which skips tiles (phase
+                             // says the same: the tile loop reads this one word for both).  (Sits in what was padding, like src_mom.)
   double         tiny_h, h_anuga_sq, xq_thresh;
   int32_t        phase;      // RDYHIP_PHASE_*
   int32_t        overwrite;  // 1: f = rhs, 0: f += rhs
@@ -602,6 +615,11 @@ __device__ __forceinline__ void courant_extra_edges(const KernelArgs &a, double 
 // of a family share the setting.  Four needs <= 128 VGPRs and 4 x tiled_lds_bytes <= 160 KB: the HR workgroup (46 KB) cannot,
 // the others are set by their own A/B timings (profiles/RESULTS_LOG.md section 15).
 constexpr int tiled_blocks_per_cu(int S, int SRC, bool hr) { return (S == 3 && SRC == 0 && !hr) ? 4 : 3; }
+// Whether an instantiation has the dynamic tile walk (KernelArgs::tile_walk) compiled in: the RHS / apply kernels of the family at
+// four workgroups per CU, where it was measured (profiles/RESULTS_LOG.md section 21).  Not its Euler-step kernels: the draw's one
+// register from the load batch to the second barrier is the 129th VGPR there (three spilled to scratch).  Not the families at
+// three, whose A/B has not been run: their kernels are the code they were.  launch_rhs asks before it sets TILE_WALK_DYNAMIC.
+constexpr bool tiled_has_dynamic_walk(int S, int SRC, bool hr, bool euler) { return tiled_blocks_per_cu(S, SRC, hr) == 4 && !euler; }
 // FNT = false: F (EULER: u_out) is stored without the non-temporal hint (RDYHIP_CONFIG_CACHED_F_STORES / states that fit the Infinity Cache)
 template <int S, int SRC, bool OVW, bool HR, bool EULER = false, bool FNT = true>
 __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(tiled_blocks_per_cu(S, SRC, HR), tiled_blocks_per_cu(S, SRC, HR)))) void swe_rhs_tiled_kernel(const KernelArgs a, const double dt, const double *__restrict__ u,
@@ -624,12 +642,41 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(tiled_bloc
   // 8 XCDs: give each XCD a contiguous range of tiles and let its workgroups
   // interleave inside it, so concurrently running tiles are neighbours and
   // their halo cells hit that XCD's own L2.
+  //      Dynamic walk (a.tile_walk, PHASE_ALL launches with xcd_chunks > 0): a workgroup's first three tiles are the static
+  // walk's -- what the pipeline holds before a draw can have come back, so that no workgroup waits for a counter at the start
+  // of the launch, when all of them would ask at once.  Every later index of the XCD's range comes from the XCD's counter
+  // (ColdArgs::tile_draw), which hands out range start + 3 per_xcd + n in order to whichever workgroup asks next: tiles are
+  // still taken in increasing order by workgroups that run side by side, and a workgroup that was held up takes fewer of
+  // them instead of finishing last.  A draw is one returning atomic add by thread 0, issued with a tile's load batch for the
+  // tile THREE ahead; it lands under the wait on the tile's streams behind the second barrier (a vmcnt(0)), where thread 0
+  // leaves it in an LDS word (in the last, unused entry of eam[]: a tile has <= TILE_MAX_REC records); all waves read the
+  // word after the next tile's first barrier, where the static walk computes idx2.  No barrier and no wait is added to the loop.
   int idx, step, hi;
+  // The counter as a GLOBAL address: through a generic pointer the draw is a flat atomic, which every lgkmcnt wait of the
+  // batch -- scalar loads, LDS -- waits for as well.
+  typedef __attribute__((address_space(1))) int *DrawCtr;
+  // (and as an address the compiler takes for divergent: for a uniform one it counts the active lanes, adds the count and
+  // works each lane's value out of the result -- which it then waits for on the spot, in the middle of the load batch)
+  // (the addend made where it is used: as a constant hipcc keeps it in a VGPR of its own for the whole launch)
+  auto draw = [](int *ctr, int word) -> int {
+    int one = 1;
+    asm volatile("" : "+v"(word), "+v"(one));
+    return __hip_atomic_fetch_add((DrawCtr)(uintptr_t)ctr + word, one, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  };
+  constexpr bool DYN   = tiled_has_dynamic_walk(S, SRC, HR, EULER);
+  const bool     dyn   = DYN && a.tile_walk == TILE_WALK_DYNAMIC;  // uniform
+  int *const draw_word = reinterpret_cast<int *>(eam + nedge - 1);
   if (a.xcd_chunks > 0) {
     const int x = blockIdx.x & 7;
     step        = gridDim.x >> 3;
     idx         = x * a.xcd_chunks + (blockIdx.x >> 3);
     hi          = min((x + 1) * a.xcd_chunks, a.n_work);
+    // Draw n is tile n behind the XCD's first 3 per_xcd: the tile index of draw 0 sits beside the word (the loop has no SGPR
+    // to keep it in), and the "draw" the first tile's batch finds is the workgroup's static third tile.
+    if (dyn && tid == 0) {
+      draw_word[0] = (int)(blockIdx.x >> 3) - step;
+      draw_word[1] = x * a.xcd_chunks + 3 * step;
+    }
   } else {
     idx  = blockIdx.x;
     step = gridDim.x;
@@ -643,8 +690,10 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(tiled_bloc
     d.e_off = v.x; d.h_off = v.y; d.c_off = v.z; d.cnt = (uint32_t)v.w;
     return d;
   };
-  auto next_valid = [&](int i) -> int {  // INTERIOR phase skips tiles with ghost-adjacent cells (wave-uniform)
-    if (a.phase == RDYHIP_PHASE_INTERIOR) {
+  // INTERIOR phase (skip) skips tiles with ghost-adjacent cells (wave-uniform).  (skip: from the kernarg segment where it is
+  // used, not a lane mask held for the launch)
+  auto next_valid = [&](int i, bool skip) -> int {
+    if (skip) {
       while (i < hi && tile_desc(tile_at(i)).halo()) i += step;
     }
     return i;
@@ -652,7 +701,12 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(tiled_bloc
 
   CourantTrack trk;
 
-  idx = next_valid(idx);
+  // (kernels with the dynamic walk read the launch's walk from the kernarg segment where they need it; the others hold the phase)
+  auto skips = [&]() -> bool {
+    if constexpr (DYN) return hot_kernargs()->a.tile_walk == TILE_WALK_STATIC_SKIP;
+    else return a.phase == RDYHIP_PHASE_INTERIOR;
+  };
+  idx = next_valid(idx, skips());
   if (idx < hi) {
     // ---- prologue: everything tile T0 needs, and the halo ids of T1
     int      tile = tile_at(idx);
@@ -686,7 +740,7 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(tiled_bloc
     // candidate without touching memory (CourantTrack); fetched a tile ahead like everything else
     int      pos_lo = load_uniform(RDY_COLD(a, e_pos), td.e_off);
     int      pos_q  = load_uniform(RDY_COLD(a, e_pos), td.e_off + min(COURANT_Q, td.ne() - 1));
-    int      idx1 = next_valid(idx + step);
+    int      idx1 = next_valid(idx + step, skips());
     int      tile1 = 0, hid1 = 0, c1 = 0;  // next tile: this thread's halo cell and own cell (local ids)
     TileDesc td1 = td;
     if (idx1 < hi) {
@@ -703,6 +757,14 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(tiled_bloc
                  "v"(c1));
 
     while (true) {
+      // the walk and its counters: asked for here, used in the load batch behind the first barrier
+      int  walk_t = TILE_WALK_STATIC;
+      int *ctr_t  = nullptr;
+      if constexpr (DYN) {
+        const HotArgs hw = hot_kernargs();
+        walk_t           = hw->a.tile_walk;
+        ctr_t            = load_uniform(&hw->a.cold->tile_draw, 0);
+      }
       const int  ne = td.ne(), nh = td.nh();
       const int  o      = td.c_off + tid;
       const bool active = tid < td.nc();
@@ -737,10 +799,19 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(tiled_bloc
       // (a) which tile comes after the next, and the ids it needs (the only dependent loads: first)
       __builtin_amdgcn_s_setprio(3);  // waves that reach their load batch issue it ahead of waves that are computing (+0.7..1 %)
       int      idx2 = hi, tile2 = 0, hid2 = 0, c2 = 0;
+      int      drawn = 0;  // thread 0, dynamic walk: the index of the tile after idx2
       TileDesc td2 = td1;
       if (idx1 < hi) {
-        idx2 = next_valid(idx1 + step);
+        if (DYN && walk_t == TILE_WALK_DYNAMIC) {
+          const int2 w = *reinterpret_cast<const int2 *>(draw_word);  // (draw, tile index of draw 0)
+          idx2         = __builtin_amdgcn_readfirstlane(w.x) + __builtin_amdgcn_readfirstlane(w.y);
+        } else {
+          if constexpr (DYN) idx2 = next_valid(idx1 + step, walk_t == TILE_WALK_STATIC_SKIP);
+          else idx2 = next_valid(idx1 + step, skips());
+        }
         if (idx2 < hi) {
+          // (not past a draw that came back beyond the range: every later one would too)
+          if (DYN && walk_t == TILE_WALK_DYNAMIC && tid == 0) drawn = draw(ctr_t, (blockIdx.x & 7) * TILE_DRAW_STRIDE);
           tile2 = tile_at(idx2);
           td2   = tile_desc(tile2);
           if (tid < td2.nh()) hid2 = a.hcells[td2.h_off + tid];
@@ -843,8 +914,15 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(tiled_bloc
       __syncthreads();
       // The tile's wait on its per-cell streams, once, ahead of every use: they were issued at the end of the previous tile
       // (the first tile's in the prologue), before that tile's stores and this tile's batch.
-      asm volatile("" ::"v"(cur.r0), "v"(cur.r1), "v"(cur.coef[0]), "v"(cur.coef[1]), "v"(cur.coef[2]), "v"(cur.coef[S - 1]), "v"(cur.dzdx),
-                   "v"(cur.dzdy), "v"(cur.nman), "v"(cur.s0), "v"(cur.s1), "v"(cur.s2));
+      if constexpr (DYN)
+        asm volatile("" ::"v"(cur.r0), "v"(cur.r1), "v"(cur.coef[0]), "v"(cur.coef[1]), "v"(cur.coef[2]), "v"(cur.coef[S - 1]), "v"(cur.dzdx),
+                     "v"(cur.dzdy), "v"(cur.nman), "v"(cur.s0), "v"(cur.s1), "v"(cur.s2), "v"(drawn));
+      else
+        asm volatile("" ::"v"(cur.r0), "v"(cur.r1), "v"(cur.coef[0]), "v"(cur.coef[1]), "v"(cur.coef[2]), "v"(cur.coef[S - 1]), "v"(cur.dzdx),
+                     "v"(cur.dzdy), "v"(cur.nman), "v"(cur.s0), "v"(cur.s1), "v"(cur.s2));
+      // That wait is a vmcnt(0): the draw issued with the batch has landed too.  Thread 0 leaves it for the next tile's batch
+      // here, behind the second barrier (under the static walk it is a zero nobody reads), and the register is free for phase 2.
+      if (DYN && tid == 0) draw_word[0] = drawn;
       // what the end of the tile reads once -- the stream arrays of the next tile's loads, the output arrays -- comes from the
       // kernarg segment here, a whole phase 2 ahead of its use
       const HotArgs    hk = hot_kernargs();
@@ -992,6 +1070,15 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(tiled_bloc
         }
       }
       if (last) break;
+    }
+  }
+  if (DYN && tid == 0 && hot_kernargs()->a.tile_walk == TILE_WALK_DYNAMIC) {
+    // Every draw of this workgroup has returned.  The workgroup that leaves last puts the nine words back to zero for the
+    // next launch (stores at the scope of the atomics): no reset launch, no host call.
+    int *const ctr = load_uniform(&hot_kernargs()->a.cold->tile_draw, 0);
+    if (atomicAdd(ctr + 8 * TILE_DRAW_STRIDE, 1) == (int)gridDim.x - 1) {
+#pragma unroll
+      for (int i = 0; i < 9; ++i) __hip_atomic_store(ctr + i * TILE_DRAW_STRIDE, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
   courant_extra_edges<HR>(a, dt, u, trk);
