@@ -719,6 +719,73 @@ int rdyhip_state_read_ptr(RDyHipOperator op, int32_t comp, const double **pinned
 int rdyhip_error_sums(RDyHipOperator op, const double *u_local, const double *d_exact, void *stream);
 int rdyhip_error_sums_get(RDyHipOperator op, RDyHipErrorSums *out);
 
+/* ---- shallow water with advected tracers ------------------------------------------
+ * The reference's PETSc tracer path -- physics.sediment (up to five size classes), salinity, temperature: shallow water with NT
+ * advected tracers, first order, semi-implicit source -- beside the SWE operator, in a kernel of its own
+ * (csrc/tracer_kernels.h).  The state is the reference's one Vec with block size n_dof = 3 + NT:
+ *     u_local  device, [num_cells][3 + NT] = (h, hu, hv, h c_0 ...), ghosts filled by the caller
+ *     f_global device, [num_owned_cells][3 + NT]
+ *   rdyhip_tracers_enable              CreatePetscTracerInteriorFluxOperator / ...BoundaryFluxOperator / ...SourceOperator
+ *                                      (src/tracer/tracer_petsc.c:295-332, 554-592, 756-785) and the n_dof-wide boundary and
+ *                                      source Vecs of CreateOperator (src/operator.c:91-129)
+ *   rdyhip_tracers_set_boundary_values SetOperatorBoundaryValues with all n_dof components, as RDySetFlowDirichletBoundaryValues
+ *                                      + RDySetSedimentDirichletBoundaryValues leave them (src/rdymms.c:745-760)
+ *   rdyhip_tracers_set_source          RDySetRegionalSedimentSource / RDySetDomain... (src/rdymms.c:630): source of tracer
+ *                                      `tracer` in `n` owned cells
+ *   rdyhip_tracers_rhs_function        OperatorRHSFunction (src/rdysetup.c:1130-1139) with ApplyTracerInteriorFlux,
+ *                                      ApplyTracerBoundaryFlux and ApplyTracerSourceSemiImplicit (tracer_petsc.c:152, 405, 617)
+ *   rdyhip_tracers_euler_step          TSStep_Euler on top of it
+ *   rdyhip_tracers_primitive_variables Operator.primitive_variables as the tracer source operator writes it (715-724)
+ *   rdyhip_tracers_get_boundary_fluxes ExtractOperatorBoundaryFluxes for the [num_edges][n_dof] flux Vec
+ *
+ * _enable allocates what the tracer path needs beyond the operator's own arrays -- boundary values [K][3 + NT], boundary fluxes
+ * [K][3 + NT], tracer sources [owned][NT], all zero-initialised -- counted in RDyHipLayoutInfo.device_bytes and freed by
+ * rdyhip_destroy; like rdyhip_output_mean_enable it may synchronise the device (as may the first
+ * rdyhip_tracers_primitive_variables, which allocates, and the host-array setters / getter, which copy).  The two evaluations
+ * enqueue one launch and never synchronise.  A second enable: RDYHIP_ERR_USER.  Refused with RDYHIP_ERR_USER before any device
+ * call: num_tracers outside 1..RDYHIP_MAX_TRACERS; an unknown `riemann`; an operator created with second_order, with
+ * well_balancing != NONE or with source_method != SEMI_IMPLICIT (the reference's PETSc tracer path has the semi-implicit source
+ * only); any boundary of type critical outflow ("CONDITION_CRITICAL_OUTFLOW not supported for tracers", tracer_petsc.c:472-474).
+ *
+ * The flow part reuses what the operator already owns: Manning's n (rdyhip_set_mannings), the [owned][3] external source
+ * (rdyhip_set_external_source: the flow components' source), the mesh tables and the Courant buckets --
+ * rdyhip_update_diagnostics / rdyhip_get_diagnostics report the most recent evaluation, of either kind.  The SWE entry points of
+ * an operator with tracers enabled behave exactly as before; their boundary values, fluxes and primitive variables are separate
+ * arrays which the tracer calls neither read nor write.
+ *
+ * rdyhip_tracers_rhs_function: F is overwritten and never read, the diagnostics start anew (one launch).  There is no accumulate
+ *   form and no phased form (RDYHIP_PHASE_ALL only).
+ * rdyhip_tracers_euler_step: u_local_out[owned rows] = fma(dt, F, u_local) for all 3 + NT components, not in place; the ghost
+ *   rows of u_local_out are left alone; with f_global == NULL F is never stored.
+ * rdyhip_tracers_primitive_variables: the [owned][3 + NT] array (h, u, v, c_0 ...): velocities in the ANUGA form
+ *   hu h / (h^2 + h_anuga^2), c_i = h c_i / h, all zero below tiny_h.  The first call allocates it and switches the storing on for
+ *   every later evaluation; until one runs it holds zeros.
+ * Arithmetic: Riemann states by ComputeRiemannVelocitiesAndConcentration (u = hu / h, c_i = h c_i / h, zero below tiny_h; no ANUGA
+ *   regularisation there); flux by ComputeTracerRoeFlux (RDYHIP_TRACER_RIEMANN_ROE) or ComputeUpwindTracerRoeFlux
+ *   (RDYHIP_TRACER_RIEMANN_UPWIND_ROE), src/tracer/tracer_roe_flux_petsc.h; Dirichlet and reflecting boundaries; erosion and
+ *   deposition with the reference's constants.  Manning's n is indexed by owned cell, as everywhere in this library (the reference
+ *   indexes by local cell there: the same on one rank).
+ * Stated differences: the flux of a boundary edge is stored for edges whose left cell is owned; rows of edges behind ghost cells
+ *   are left as they are.  There is no accumulated-flux array (the reference's tracer boundary operator keeps none).  On a rank
+ *   with ghost cells the Courant diagnostic covers the edges of the owned cells with len / area_self only: edges between two
+ *   ghosts, and the len / area of a ghost that is the smaller cell of a cut edge, do not enter.
+ * Ghost rows of 3 + NT values travel through rdyhip_pack_rows / rdyhip_unpack_rows; the halo object's fused steps, the output
+ * means, the time series and the read-out cover the three flow components of the SWE state only.
+ * Every argument error (a null operator, tracers not enabled, a null array where one is needed, a tracer or boundary index out of
+ * range, num_edges not the boundary's) is RDYHIP_ERR_USER and is reported before any device call.  A rank that owns nothing
+ * launches nothing and succeeds. */
+#define RDYHIP_MAX_TRACERS 7                 /* MAX_NUM_TRACERS: 5 sediment classes + salinity + temperature (CMakeLists.txt:12-22) */
+#define RDYHIP_TRACER_RIEMANN_ROE 0          /* ComputeTracerRoeFlux */
+#define RDYHIP_TRACER_RIEMANN_UPWIND_ROE 1   /* ComputeUpwindTracerRoeFlux (RIEMANN_UPWIND_ROE) */
+int rdyhip_tracers_enable(RDyHipOperator op, int32_t num_tracers, int32_t riemann);
+int rdyhip_tracers_info(RDyHipOperator op, int32_t *num_tracers, int32_t *riemann);            /* 0 tracers: not enabled */
+int rdyhip_tracers_set_boundary_values(RDyHipOperator op, int32_t boundary, int32_t num_edges, const double *values /* host [num_edges][3+NT] */);
+int rdyhip_tracers_set_source(RDyHipOperator op, int32_t tracer, int32_t n, const int32_t *owned_cell_ids /* NULL: 0..n-1 */, const double *values /* host */);
+int rdyhip_tracers_rhs_function(RDyHipOperator op, double dt, const double *u_local, double *f_global, void *stream);
+int rdyhip_tracers_euler_step(RDyHipOperator op, double dt, const double *u_local, double *u_local_out, double *f_global /* may be NULL */, void *stream);
+int rdyhip_tracers_primitive_variables(RDyHipOperator op, const double **device_ptr, int64_t *num_values);
+int rdyhip_tracers_get_boundary_fluxes(RDyHipOperator op, int32_t boundary, int32_t num_edges, double *fluxes /* host [num_edges][3+NT] */);
+
 /* ---- introspection ----------------------------------------------------------
  * numbers describing the device layout, for DESIGN.md / bench.py */
 typedef struct {

@@ -128,6 +128,14 @@ SYMBOLS = {
     "rdyhip_state_read_ptr": (C.c_int, [_H, C.c_int32, C.POINTER(c_double_p)]),
     "rdyhip_error_sums": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rdyhip_error_sums_get": (C.c_int, [_H, C.POINTER(RDyHipErrorSums)]),
+    "rdyhip_tracers_enable": (C.c_int, [_H, C.c_int32, C.c_int32]),
+    "rdyhip_tracers_info": (C.c_int, [_H, c_int32_p, c_int32_p]),
+    "rdyhip_tracers_set_boundary_values": (C.c_int, [_H, C.c_int32, C.c_int32, c_double_p]),
+    "rdyhip_tracers_set_source": (C.c_int, [_H, C.c_int32, C.c_int32, c_int32_p, c_double_p]),
+    "rdyhip_tracers_rhs_function": (C.c_int, [_H, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rdyhip_tracers_euler_step": (C.c_int, [_H, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rdyhip_tracers_primitive_variables": (C.c_int, [_H, C.POINTER(C.c_void_p), c_int64_p]),
+    "rdyhip_tracers_get_boundary_fluxes": (C.c_int, [_H, C.c_int32, C.c_int32, c_double_p]),
     "rdyhip_halo_create": (C.c_int, [_H, C.c_void_p, C.c_int32, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p, C.POINTER(C.c_void_p)]),
     "rdyhip_halo_destroy": (C.c_int, [C.POINTER(C.c_void_p)]),
     "rdyhip_halo_overlaps": (C.c_int32, [C.c_void_p]),

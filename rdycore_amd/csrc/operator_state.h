@@ -223,6 +223,13 @@ struct RDyHipOperator_s : LayoutCounts {
   std::vector<int32_t> h_bghost;   // the boundary edges whose left cell is a ghost
   // rdyhip_state_read_* / rdyhip_error_sums (declared after `stage`: its copy stream outlives these buffers)
   Readout readout;
+  // rdyhip_tracers_* (tracer_kernels.h): N = 3 + n_tracers values per row.  Boundary values and fluxes [K][N] and the tracer
+  // sources [n_owned][n_tracers] are allocated by rdyhip_tracers_enable, the primitive variables [n_owned][N] by the first
+  // rdyhip_tracers_primitive_variables, from which on every tracer evaluation stores them.
+  int32_t              n_tracers = 0, tracer_riemann = 0;   // 0 tracers: not enabled
+  DevBuf<double>       d_tr_bvalues, d_tr_bflux, d_tr_src, d_tr_pv;
+  bool                 tr_pv_wanted = false;
+  std::vector<int32_t> h_btype;    // [K] condition type of every boundary edge (the tracer path refuses critical outflow)
 
   int64_t device_bytes = 0;
 };

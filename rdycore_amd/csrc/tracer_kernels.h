@@ -1,0 +1,265 @@
+// Shallow water with advected tracers (sediment classes, salinity, temperature) for gfx950: the first-order right-hand side
+// of the reference's PETSc tracer path (src/tracer/tracer_petsc.c, src/tracer/tracer_roe_flux_petsc.h) in one kernel of the
+// cell-centric form (swe_rhs_kernel, swe_kernels.h): one thread = one owned cell, every edge of the cell evaluated by that
+// thread in slot order (= the reference's loop order), so the per-cell sum has a fixed order and needs no atomics.
+//
+// The state is [cell][3 + NT] = (h, hu, hv, h c_0 ...): the reference's one Vec with block size n_dof.  NT is a template
+// argument: the rows, the accumulators and the concentrations are per-thread arrays with compile-time indices and live in
+// registers (a run-time tracer count would put them in scratch).  A row's 3 + NT doubles are loaded and stored back to back.
+//
+// The flow part reuses the operator's own tables through KernelArgs / ColdArgs (slot tables, Manning n, the [owned][3]
+// external source, the Courant buckets); what only this path has travels in TracerArgs.  Nothing in swe_device.h,
+// swe_kernels.h or muscl_kernels.h is changed: their inline functions are called, roe_flux() is restated here because the
+// tracer flux needs the eigenvalues and wave strengths it does not hand out.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "rdyhip.h"
+#include "swe_device.h"
+#include "swe_kernels.h"
+
+namespace rdyhip {
+
+// what the tracer kernel reads and writes beyond KernelArgs (N = 3 + NT values per row)
+struct TracerArgs {
+  const double *bvalues;  // [K][N] Dirichlet values (h, hu, hv, h c_0 ...) of boundary edge k
+  double       *bflux;    // [K][N] flux through boundary edge k (edges whose left cell is owned)
+  const double *src;      // [n_owned][NT] tracer sources
+  double       *pv;       // [n_owned][N] (h, u, v, c_0 ...) or nullptr: nobody has asked for them
+  double       *f;        // [n_owned][N] or nullptr (an Euler step whose caller wants no F)
+  double       *u_out;    // [num_cells][N] or nullptr: owned rows = fma(dt, F, u)
+};
+
+// DENSITY_OF_WATER and the erosion / deposition constants of ApplyTracerSourceSemiImplicit (tracer_petsc.c:633-637)
+constexpr double TRACER_RHO_WATER       = 1000.0;
+constexpr double TRACER_KP              = 0.001;
+constexpr double TRACER_SETTLING        = 0.01;
+constexpr double TRACER_TAU_EROSION     = 0.1;
+constexpr double TRACER_TAU_DEPOSITION  = 1000.0;
+
+// ComputeRiemannVelocitiesAndConcentration (tracer_petsc.c:105-128) for the concentrations of one state: zero below
+// tiny_h, else h c_i / h with the reciprocal taken once.  (The velocities are riemann_side(..., h_anuga_sq = 0).)
+template <int NT>
+__device__ __forceinline__ void tracer_concentrations(double h, const double *hc, double tiny_h, double *c) {
+  const double inv = rdy_rcp(h);
+#pragma unroll
+  for (int j = 0; j < NT; ++j) c[j] = (h < tiny_h) ? 0.0 : hc[j] * inv;
+}
+
+// ComputeTracerRoeFlux / ComputeUpwindTracerRoeFlux (tracer_roe_flux_petsc.h:17-119, 129-206) for one edge.  The flow
+// components are ComputeSWERoeFlux in the arithmetic of roe_flux() (swe_device.h), operation for operation; tracer j adds
+//   Roe:     cihat = (sqrt(hl) cl + sqrt(hr) cr) / (sqrt(hl) + sqrt(hr)),  dW_j = (cr hr - cl hl) - cihat (hr - hl),
+//            flux_j = 0.5 (hl uperp_l cl + hr uperp_r cr) - 0.5 (cihat A0 dW0 + cihat A2 dW2 + A1 dW_j)
+//   upwind:  flux_j = F_h (F_h >= 0 ? cl : cr), F_h the Roe mass flux
+// fl[0..2] flow, fl[3..] tracers; returns amax.
+template <int NT, bool UPWIND>
+__device__ __forceinline__ double tracer_roe_flux(const RiemannSide &L, const RiemannSide &R, const double *cl_, const double *cr_, double sn, double cn,
+                                                  double *fl) {
+  const double hl = L.h, ul = L.u, vl = L.v, hr = R.h, ur = R.u, vr = R.v;
+  const double duml = L.sqh, dumr = R.sqh, cl = L.c, cr = R.c;
+  const double hhat    = duml * dumr;
+  const double inv_sum = rdy_rcp(duml + dumr);
+  const double uhat    = sum_of_products(duml, ul, dumr, ur) * inv_sum;
+  const double vhat    = sum_of_products(duml, vl, dumr, vr) * inv_sum;
+  const SqrtPair cp       = rdy_sqrt_rsqrt(0.5 * GRAVITY * (hl + hr));
+  const double   chat     = cp.s;
+  const double   inv_chat = cp.r;
+  const double uperp   = sum_of_products(uhat, cn, vhat, sn);
+
+  const double dh     = hr - hl;
+  const double du     = ur - ul;
+  const double dv     = vr - vl;
+  const double dupar  = -du * sn + dv * cn;
+  const double duperp = du * cn + dv * sn;
+
+  const double r10 = uhat - chat * cn, r11 = -sn, r12 = uhat + chat * cn;
+  const double r20 = vhat - chat * sn, r21 = cn, r22 = vhat + chat * sn;
+
+  const double uperpl = ul * cn + vl * sn;
+  const double uperpr = ur * cn + vr * sn;
+  double       a1     = fabs(uperp - chat);
+  const double a2     = fabs(uperp);
+  double       a3     = fabs(uperp + chat);
+
+  // critical flow fix
+  const double da1 = fmax(0.0, 2.0 * ((uperpr - cr) - (uperpl - cl)));
+  if (a1 < da1) a1 = 0.5 * (a1 * a1 / da1 + da1);
+  const double da3 = fmax(0.0, 2.0 * ((uperpr + cr) - (uperpl + cl)));
+  if (a3 < da3) a3 = 0.5 * (a3 * a3 / da3 + da3);
+
+  const double t   = hhat * duperp * inv_chat;
+  const double dw0 = 0.5 * (dh - t);
+  const double dw1 = hhat * dupar;
+  const double dw2 = 0.5 * (dh + t);
+
+  const double gh2l = 0.5 * GRAVITY * hl * hl, gh2r = 0.5 * GRAVITY * hr * hr;
+  const double ql = uperpl * hl, qr = uperpr * hr;
+  const double fl1 = ul * ql + gh2l * cn;
+  const double fl2 = vl * ql + gh2l * sn;
+  const double fr1 = ur * qr + gh2r * cn;
+  const double fr2 = vr * qr + gh2r * sn;
+
+  const double w0 = a1 * dw0, w1 = a2 * dw1, w2 = a3 * dw2;
+  fl[0] = 0.5 * (ql + qr - w0 - 0.0 * w1 - w2);
+  fl[1] = 0.5 * (fl1 + fr1 - r10 * w0 - r11 * w1 - r12 * w2);
+  fl[2] = 0.5 * (fl2 + fr2 - r20 * w0 - r21 * w1 - r22 * w2);
+#pragma unroll
+  for (int j = 0; j < NT; ++j) {
+    if (UPWIND) {
+      fl[3 + j] = fl[0] * (fl[0] >= 0.0 ? cl_[j] : cr_[j]);
+    } else {
+      const double cihat = sum_of_products(duml, cl_[j], dumr, cr_[j]) * inv_sum;
+      const double dwj   = (cr_[j] * hr - cl_[j] * hl) - cihat * dh;
+      fl[3 + j]          = 0.5 * (ql * cl_[j] + qr * cr_[j] - cihat * w0 - cihat * w2 - a2 * dwj);
+    }
+  }
+  return chat + fabs(uperp);
+}
+
+// One thread = one owned cell: the cell's own row is prepared once, its up to S slots are walked in slot order, the source
+// epilogue of ApplyTracerSourceSemiImplicit (tracer_petsc.c:617-737) and the stores follow; the Courant bucket goes through
+// block_courant_reduce with the `pos` table, so ties resolve as in swe_rhs_kernel.  PHASE_ALL, f = F(u) only.
+template <int S, int NT, bool UPWIND>
+__global__ __launch_bounds__(BLOCK) void tracer_rhs_kernel(const KernelArgs a, const TracerArgs t, const double dt, const double *__restrict__ u) {
+  constexpr int N = 3 + NT;
+  const int     i = xcd_block(a.xcd_chunks) * BLOCK + threadIdx.x;
+
+  double best      = 0.0;
+  int    best_slot = -1;
+  int    o         = 0;
+
+  const bool active = i < a.n_work;
+  if (active) {
+    o = i;
+    const int32_t *nbr = RDY_COLD(a, nbr), *btype = RDY_COLD(a, btype);
+    const double  *cn_ = RDY_COLD(a, cn), *sn_ = RDY_COLD(a, sn);
+    int32_t        id[S];
+#pragma unroll
+    for (int s = 0; s < S; ++s) id[s] = nbr[s * a.stride + o];
+
+    const int64_t c = a.o2l ? a.o2l[o] : o;
+    double        own[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) own[k] = u[N * c + k];
+    const RiemannSide self = riemann_side(own[0], own[1], own[2], a.tiny_h, 0.0);
+    double            self_c[NT];
+    tracer_concentrations<NT>(own[0], own + 3, a.tiny_h, self_c);
+
+    double acc[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) acc[k] = 0.0;
+
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      const int32_t nid = id[s];
+      if (nid == NBR_EMPTY) continue;  // a triangle in the 4-slot layout, or an outer edge that belongs to no boundary
+      const double cn   = cn_[s * a.stride + o];
+      const double sn   = sn_[s * a.stride + o];
+      const double coef = a.coef[s * a.stride + o];
+      const double cfac = fabs(coef);  // len / area_self: the max over an edge's two cells is len / min(area_l, area_r)
+      double       fl[N], amax;
+      bool         wet;
+      if (nid >= 0) {
+        const int64_t n = nid & NBR_MASK;
+        double        oth[N];
+#pragma unroll
+        for (int k = 0; k < N; ++k) oth[k] = u[N * n + k];
+        const RiemannSide other = riemann_side(oth[0], oth[1], oth[2], a.tiny_h, 0.0);
+        double            other_c[NT];
+        tracer_concentrations<NT>(oth[0], oth + 3, a.tiny_h, other_c);
+        const bool  self_left = coef < 0.0;
+        RiemannSide L, R;
+        L.h = self_left ? self.h : other.h;        R.h = self_left ? other.h : self.h;
+        L.u = self_left ? self.u : other.u;        R.u = self_left ? other.u : self.u;
+        L.v = self_left ? self.v : other.v;        R.v = self_left ? other.v : self.v;
+        L.sqh = self_left ? self.sqh : other.sqh;  R.sqh = self_left ? other.sqh : self.sqh;
+        L.c = self_left ? self.c : other.c;        R.c = self_left ? other.c : self.c;
+        double cl[NT], cr[NT];
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+          cl[j] = self_left ? self_c[j] : other_c[j];
+          cr[j] = self_left ? other_c[j] : self_c[j];
+        }
+        amax = tracer_roe_flux<NT, UPWIND>(L, R, cl, cr, sn, cn, fl);
+        wet  = !(R.h < a.tiny_h && L.h < a.tiny_h);
+      } else {
+        // ApplyTracerBoundaryFlux (tracer_petsc.c:405-525): the cell is the left one.  Critical outflow is refused at
+        // rdyhip_tracers_enable (472-474), so a type that is not Dirichlet is reflecting.
+        const int64_t k = -1 - nid;
+        RiemannSide   R;
+        double        cr[NT];
+        if (btype[k] == RDYHIP_CONDITION_DIRICHLET) {
+          double bv[N];
+#pragma unroll
+          for (int q = 0; q < N; ++q) bv[q] = t.bvalues[N * k + q];
+          R = riemann_side(bv[0], bv[1], bv[2], a.tiny_h, 0.0);
+          tracer_concentrations<NT>(bv[0], bv + 3, a.tiny_h, cr);
+        } else {  // ApplyTracerReflectingBC (362-395): h and c_i copied, the velocity mirrored
+          const double dum1 = sn * sn - cn * cn;
+          const double dum2 = 2.0 * sn * cn;
+          R.h               = self.h;
+          R.u               = self.u * dum1 - self.v * dum2;
+          R.v               = -self.u * dum2 - self.v * dum1;
+          R.sqh             = self.sqh;
+          R.c               = self.c;
+#pragma unroll
+          for (int j = 0; j < NT; ++j) cr[j] = self_c[j];
+        }
+        amax = tracer_roe_flux<NT, UPWIND>(self, R, self_c, cr, sn, cn, fl);
+        wet  = !(self.h < a.tiny_h && R.h < a.tiny_h);
+#pragma unroll
+        for (int q = 0; q < N; ++q) t.bflux[N * k + q] = fl[q];
+      }
+      if (wet) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) acc[k] += fl[k] * coef;
+        const double cnum = amax * cfac * dt;
+        if (cnum > best) {
+          best      = cnum;
+          best_slot = s;
+        }
+      }
+    }
+
+    // sources: bed slope, semi-implicit friction on the pre-source momentum sums, erosion - deposition for wet cells
+    const double h = own[0];
+    const double n = a.mannings[o];
+    double       bedx, bedy, tbx, tby;
+    cell_source<RDYHIP_SOURCE_SEMI_IMPLICIT>(a, dt, h, own[1], own[2], acc[1], acc[2], a.dzdx[o], a.dzdy[o], n, bedx, bedy, tbx, tby);
+    double F[N];
+    F[0] = acc[0] + a.extsrc[3 * (int64_t)o + 0];
+    F[1] = acc[1] + (-bedx - tbx + a.extsrc[3 * (int64_t)o + 1]);
+    F[2] = acc[2] + (-bedy - tby + a.extsrc[3 * (int64_t)o + 2]);
+    const bool   cell_wet = h >= a.tiny_h;
+    const double Cd       = GRAVITY * (n * n) * rcbrt(h);
+    const double tau_b    = 0.5 * TRACER_RHO_WATER * Cd * (self.u * self.u + self.v * self.v);  // h >= tiny_h: self.u = hu / h
+    const double ei       = TRACER_KP * (tau_b - TRACER_TAU_EROSION) / TRACER_TAU_EROSION;
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+      const double di = TRACER_SETTLING * self_c[j] * (1.0 - tau_b / TRACER_TAU_DEPOSITION);
+      F[3 + j]        = cell_wet ? acc[3 + j] + ((ei - di) + t.src[NT * (int64_t)o + j]) : acc[3 + j];
+    }
+
+    if (t.f) {
+#pragma unroll
+      for (int k = 0; k < N; ++k) RDY_ST(&t.f[N * (int64_t)o + k], F[k]);
+    }
+    // primitive variables (tracer_petsc.c:715-724): the regularised velocities, c_i = h c_i / h, all zero below tiny_h
+    if (t.pv) {
+      const RiemannSide p = riemann_side(h, own[1], own[2], a.tiny_h, a.h_anuga_sq);
+      RDY_ST(&t.pv[N * (int64_t)o + 0], h);
+      RDY_ST(&t.pv[N * (int64_t)o + 1], p.u);
+      RDY_ST(&t.pv[N * (int64_t)o + 2], p.v);
+#pragma unroll
+      for (int j = 0; j < NT; ++j) RDY_ST(&t.pv[N * (int64_t)o + 3 + j], self_c[j]);
+    }
+    if (t.u_out) {
+#pragma unroll
+      for (int k = 0; k < N; ++k) RDY_ST(&t.u_out[N * c + k], fma(dt, F[k], own[k]));
+    }
+  }
+  block_courant_reduce<BLOCK>(a, best, RDY_COLD(a, pos), (best_slot < 0 ? 0 : best_slot) * a.stride + o);
+}
+
+}  // namespace rdyhip

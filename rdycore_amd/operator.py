@@ -31,6 +31,8 @@ PHASE_ALL, PHASE_INTERIOR, PHASE_HALO = 0, 1, 2
 OUTPUT_SOLUTION, OUTPUT_PRIMITIVE_VARIABLES, OUTPUT_SOURCES = 1, 2, 4   # RDYHIP_OUTPUT_*: the time-averaged output fields
 SERIES_OBSERVATIONS, SERIES_BOUNDARY_FLUXES = 1, 2                      # RDYHIP_SERIES_*: the time series kept on the device
 COMPONENT_H, COMPONENT_HU, COMPONENT_HV = 1, 2, 4                       # RDYHIP_COMPONENT_*: the planes of the state read-out
+MAX_TRACERS = 7                                                         # RDYHIP_MAX_TRACERS
+TRACER_RIEMANN_ROE, TRACER_RIEMANN_UPWIND_ROE = 0, 1                    # RDYHIP_TRACER_RIEMANN_*
 
 
 @dataclasses.dataclass
@@ -410,6 +412,77 @@ class Operator:
         s = _lib.RDyHipErrorSums()
         _lib.check(lib.rdyhip_error_sums_get(self._h, C.byref(s)))
         return {"l1": np.array(s.l1[:]), "l2_squared": np.array(s.l2_squared[:]), "linf": np.array(s.linf[:]), "area": float(s.area)}
+
+    # -- shallow water with advected tracers (src/tracer/tracer_petsc.c): state [num_cells, 3 + NT] = (h, hu, hv, h c_0 ...) --------
+    num_tracers = 0
+
+    def enable_tracers(self, n: int, riemann: int = TRACER_RIEMANN_ROE):
+        """rdyhip_tracers_enable: the tracer path with `n` tracers (1..7) and the Roe (0) or upwind Roe (1) tracer flux; allocates
+        its boundary values / fluxes [K, 3 + n] and tracer sources [owned, n], all zero"""
+        _lib.check(_lib.load().rdyhip_tracers_enable(self._h, int(n), int(riemann)))
+        self.num_tracers = int(n)
+
+    def tracers_info(self) -> Tuple[int, int]:
+        """rdyhip_tracers_info: (number of tracers -- 0: not enabled --, tracer Riemann solver)"""
+        n, r = C.c_int32(), C.c_int32()
+        _lib.check(_lib.load().rdyhip_tracers_info(self._h, C.byref(n), C.byref(r)))
+        return n.value, r.value
+
+    def _check_tracer_state(self, t, name: str, cells: int, optional: bool = False):
+        if optional and t is None:
+            return
+        n = 3 + self.num_tracers
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == n * cells):
+            raise RDyHipError(83, f"{name} must be a contiguous float64 device tensor of {cells} cells x {n}")
+
+    def tracers_set_boundary_values(self, boundary: int, values):
+        """values[e, :] = (h, hu, hv, h c_0 ...) of boundary edge e, all 3 + NT components (rdyhip_tracers_set_boundary_values)"""
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        ne = v.shape[0] if v.ndim == 2 and v.shape[1] == 3 + self.num_tracers else -1
+        _lib.check(_lib.load().rdyhip_tracers_set_boundary_values(self._h, int(boundary), int(ne), v.ctypes.data_as(_lib.c_double_p) if v.size else None))
+
+    def tracers_set_source(self, tracer: int, values, owned_cell_ids=None):
+        """rdyhip_tracers_set_source: the source of tracer `tracer` in the owned cells `owned_cell_ids` (None: cells 0 .. n - 1)"""
+        v = np.ascontiguousarray(values, dtype=np.float64).ravel()
+        ip = None
+        if owned_cell_ids is not None:
+            ids = np.ascontiguousarray(owned_cell_ids, dtype=np.int32).ravel()
+            if ids.size != v.size:
+                raise RDyHipError(60, f"size ({v.size}) does not match the region size ({ids.size})")
+            ip = ids.ctypes.data_as(_lib.c_int32_p)
+        _lib.check(_lib.load().rdyhip_tracers_set_source(self._h, int(tracer), int(v.size), ip, v.ctypes.data_as(_lib.c_double_p) if v.size else None))
+
+    def tracers_rhs_function(self, dt: float, u_local: torch.Tensor, f_global: torch.Tensor):
+        """rdyhip_tracers_rhs_function: f_global [owned, 3 + NT] = F(u_local [num_cells, 3 + NT]), diagnostics reset, one launch"""
+        self._check_tracer_state(u_local, "u_local", self.mesh.num_cells)
+        self._check_tracer_state(f_global, "f_global", self.mesh.num_owned_cells)
+        _lib.check(_lib.load().rdyhip_tracers_rhs_function(self._h, float(dt), _ptr(u_local), _ptr(f_global), _stream()))
+
+    def tracers_euler_step(self, dt: float, u_local: torch.Tensor, u_out: torch.Tensor, f_global: Optional[torch.Tensor] = None):
+        """rdyhip_tracers_euler_step: u_out[owned rows] = fma(dt, F, u_local), not in place; f_global=None: F is never stored"""
+        self._check_tracer_state(u_local, "u_local", self.mesh.num_cells)
+        self._check_tracer_state(u_out, "u_out", self.mesh.num_cells)
+        self._check_tracer_state(f_global, "f_global", self.mesh.num_owned_cells, optional=True)
+        _lib.check(_lib.load().rdyhip_tracers_euler_step(self._h, float(dt), _ptr(u_local), _ptr(u_out),
+                                                         _ptr(f_global) if f_global is not None else None, _stream()))
+
+    def tracers_primitive_variables(self) -> torch.Tensor:
+        """rdyhip_tracers_primitive_variables: [owned, 3 + NT] (h, u, v, c_0 ...) as a view of the device array; stored by every
+        tracer evaluation after the first request, zeros until one has run"""
+        p, n = C.c_void_p(), C.c_int64()
+        _lib.check(_lib.load().rdyhip_tracers_primitive_variables(self._h, C.byref(p), C.byref(n)))
+        ncomp = 3 + self.num_tracers
+        if n.value == 0:
+            return torch.zeros((0, ncomp), dtype=torch.float64, device="cuda")
+        return torch.as_tensor(_DeviceArray(p.value, (n.value,), self), device="cuda").view(-1, ncomp)
+
+    def tracers_boundary_fluxes(self, boundary: int) -> np.ndarray:
+        """rdyhip_tracers_get_boundary_fluxes: [num_edges, 3 + NT] fluxes through the edges of `boundary` (rows of edges whose
+        left cell is a ghost are not written)"""
+        n = self.mesh.boundaries[boundary].num_edges if 0 <= boundary < len(self.mesh.boundaries) else 0
+        out = np.zeros((n, 3 + self.num_tracers))
+        _lib.check(_lib.load().rdyhip_tracers_get_boundary_fluxes(self._h, int(boundary), n, out.ctypes.data_as(_lib.c_double_p) if out.size else None))
+        return out
 
     # -- second order: ComputeLeastSquaresGradients for the owned cells (src/operator_fluxes_ceed.c:998-1042)
     def compute_gradients(self, u_local: torch.Tensor, phase: int = PHASE_ALL):

@@ -1,0 +1,353 @@
+"""GPU: shallow water with advected tracers (rdyhip_tracers_*, csrc/tracer_kernels.h) against tests/tracer_reference.py, the numpy
+restatement that tests/test_tracers_cpu.py ties to the C oracle, to a hand-derived answer and to the reference's sediment
+convergence study.
+
+The shapes are chosen where the indexing can go wrong, not for size: 30 cells (under one wave), 270 (one workgroup and a partial
+wave), the 44 quads of planar_dam_10x5.msh, the mixed quad / triangle mesh (empty fourth slots), one rank's part of a random
+partition (about 1 000 owned cells with ghosts interleaved: the owned -> local table is used), and a rank that owns nothing.
+States are seeded and random: cells at h = 0, cells between 0 and tiny_h, thin films, deep and supercritical water, wet/dry
+fronts (region-blocked on the 270-cell mesh), Dirichlet and reflecting boundaries, Manning's n, bed slopes, water, momentum and
+tracer sources.  Bars: 1e-10 (helpers.rel_linf, what test_gpu_parity.py holds the RHS to) for F, the primitive variables and
+the boundary fluxes, 1e-12 for the Courant number, exact ids, bits for the Euler step and for the undisturbed SWE path."""
+import ctypes as C
+import functools
+import os
+from fractions import Fraction
+
+import numpy as np
+import pytest
+
+import tracer_reference as TR
+from helpers import rel_linf
+from random_cases import random_case, random_partition_mesh
+from rdycore_amd import _lib
+from rdycore_amd import cases as CS
+from rdycore_amd import mesh as M
+from rdycore_amd.operator import (Operator, RDyFlowConfig, RDyHipError, SOURCE_IMPLICIT_XQ2018, TRACER_RIEMANN_ROE, TRACER_RIEMANN_UPWIND_ROE,
+                                  WELL_BALANCING_HR)
+from test_tracers_cpu import reference_make_apply, sediment_run_level, tracer_case
+
+pytestmark = pytest.mark.gpu
+
+TOL = 1e-10
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+MESHES = ["tri-30", "tri-270", "quad-44", "mixed", "part-o2l"]
+
+
+def _torch():
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a HIP device"
+    return torch
+
+
+def _bathymetry(x, y):
+    return 0.2 * np.sin(0.6 * x) * np.cos(0.4 * y)
+
+
+@functools.lru_cache(maxsize=None)
+def _mesh(name):
+    if name == "part-o2l":
+        mesh = random_partition_mesh(np.random.default_rng(415), "tri", 28, 30)
+        assert 800 <= mesh.num_owned_cells <= 1200 and mesh.num_cells > mesh.num_owned_cells
+        assert (np.asarray(mesh.cell_owned_to_local) != np.arange(mesh.num_owned_cells)).any()
+        return mesh
+    if name == "quad-44":
+        mesh = CS.ex2b_case(os.path.join(GOLDEN, "planar_dam_10x5.msh")).mesh
+        assert mesh.num_cells == 44 and (mesh.cell_nverts == 4).all()
+        return mesh
+    if name == "mixed":
+        mesh = CS.mixed_elements_case(os.path.join(GOLDEN, "mixed")).mesh
+        assert (mesh.cell_nverts == 3).any() and (mesh.cell_nverts == 4).any()
+        return mesh
+    nx, ny = {"tri-30": (5, 3), "tri-270": (9, 15)}[name]
+    mesh = M.structured_tri_mesh(nx, ny, 1.0, zfunc=_bathymetry)
+    assert mesh.num_owned_cells == int(name.split("-")[1])
+    return mesh
+
+
+def _empty_mesh():
+    xyz, conn, _, _ = M.structured_tri_connectivity(3, 2)
+    mesh = M.build_mesh(xyz, conn, is_owned=np.zeros(conn.shape[0], dtype=np.int32), boundary_classifier=M.box_side_boundaries(0, 3, 0, 2))
+    assert mesh.num_owned_cells == 0 and mesh.num_cells == 12
+    return mesh
+
+
+@functools.lru_cache(maxsize=None)
+def _case(name, nt, riemann):
+    """(case, reference with its results of ONE apply, state, F): computed once, shared, left unchanged"""
+    rng = np.random.default_rng(1000 + 10 * nt + riemann + len(name))
+    mesh = _mesh(name)
+    case, ref, u = tracer_case(rng, mesh, nt, riemann, h_anuga=1e-3 if name == "quad-44" else 0.0, region_block=16 if name == "tri-270" else 0)
+    h = u[:, 0]
+    assert (h == 0.0).any() and (h >= case.config.tiny_h).any()
+    if mesh.num_cells >= 100:
+        assert ((h > 0.0) & (h < case.config.tiny_h)).any()
+    F = ref.apply(case.dt, u)
+    assert np.isfinite(F).all() and np.abs(F[:, 3:]).max() > 0.0
+    for a in (u, F, ref.primitive_variables):
+        a.setflags(write=False)
+    return case, ref, u, F
+
+
+def _operator(case, ref, nt, riemann):
+    """the device operator of a case with the tracer path enabled and every input of the reference set"""
+    op = CS.create_operator(case)
+    op.enable_tracers(nt, riemann)
+    assert op.tracers_info() == (nt, riemann)
+    for j in range(nt):
+        op.tracers_set_source(j, ref.tracer_sources[:, j])
+    for b in range(len(case.mesh.boundaries)):
+        if case.mesh.boundaries[b].num_edges:
+            op.tracers_set_boundary_values(b, ref.boundary_values[b])
+    return op
+
+
+def _dev(a):
+    return _torch().tensor(np.ascontiguousarray(a), dtype=_torch().float64, device="cuda")
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
+
+
+COMBOS = [(1, TRACER_RIEMANN_ROE), (2, TRACER_RIEMANN_UPWIND_ROE), (7, TRACER_RIEMANN_ROE), (7, TRACER_RIEMANN_UPWIND_ROE)]
+
+
+@pytest.mark.parametrize("nt,riemann", COMBOS)
+@pytest.mark.parametrize("name", MESHES)
+def test_rhs_primitive_variables_boundary_fluxes_and_courant(name, nt, riemann):
+    torch = _torch()
+    case, ref, u, F = _case(name, nt, riemann)
+    mesh = case.mesh
+    op = _operator(case, ref, nt, riemann)
+    pv = op.tracers_primitive_variables()
+    assert pv.shape == (mesh.num_owned_cells, 3 + nt)
+    f = torch.full((mesh.num_owned_cells, 3 + nt), float("nan"), dtype=torch.float64, device="cuda")   # every owned row is written
+    op.tracers_rhs_function(case.dt, _dev(u), f)
+    torch.cuda.synchronize()
+    got = f.cpu().numpy()
+    assert np.isfinite(got).all()
+    err, perr = rel_linf(got, F), rel_linf(pv.cpu().numpy(), ref.primitive_variables)
+    print(f"{name} nt={nt} riemann={riemann}: F {err:.3e}, pv {perr:.3e}")
+    assert err <= TOL and perr <= TOL
+    if name == "part-o2l":          # F and pv only: boundary fluxes behind ghosts and the ghost edges' Courant numbers are stated differences
+        op.destroy()
+        return
+    for b, bnd in enumerate(mesh.boundaries):
+        bf, want = op.tracers_boundary_fluxes(b), ref.boundary_fluxes[b]
+        ok = np.isfinite(want).all(axis=1)          # an edge dry on both sides: 0 / 0 in the reference's flux, which it then discards
+        assert rel_linf(bf[ok], want[ok]) <= TOL
+    op.update_diagnostics()
+    d = op.get_diagnostics()
+    cmax, edge, cell = ref.courant
+    assert cmax > 0.0 and abs(d.max_courant_num - cmax) <= 1e-12 * max(1.0, cmax)
+    ec = np.sort(ref.edge_courant[np.isfinite(ref.edge_courant)])
+    assert ec[-1] - ec[-2] > 1e-9 * ec[-1], "the state has a near tie: choose another seed"
+    assert (d.global_edge_id, d.global_cell_id) == (int(mesh.edge_global_ids[edge]), int(mesh.cell_global_ids[cell]))
+    op.destroy()
+
+
+@pytest.mark.parametrize("name,nt,riemann", [("tri-270", 2, TRACER_RIEMANN_UPWIND_ROE), ("part-o2l", 7, TRACER_RIEMANN_ROE), ("mixed", 1, TRACER_RIEMANN_ROE)])
+def test_euler_step_is_one_fused_multiply_add_of_the_rhs(name, nt, riemann):
+    torch = _torch()
+    case, ref, u, _ = _case(name, nt, riemann)
+    mesh, dt, n = case.mesh, case.dt, 3 + nt
+    op = _operator(case, ref, nt, riemann)
+    ud = _dev(u)
+    f = torch.empty((mesh.num_owned_cells, n), dtype=torch.float64, device="cuda")
+    op.tracers_rhs_function(dt, ud, f)
+    Fd = f.cpu().numpy()
+    own = np.asarray(mesh.cell_owned_to_local)
+    want = np.array([[float(Fraction(dt) * Fraction(float(Fd[o, k])) + Fraction(float(u[c, k]))) for k in range(n)] for o, c in enumerate(own)])
+    ghost = np.setdiff1d(np.arange(mesh.num_cells), own)
+    for with_f in (True, False):
+        out = torch.full((mesh.num_cells, n), -777.0, dtype=torch.float64, device="cuda")
+        f2 = torch.full((mesh.num_owned_cells, n), float("nan"), dtype=torch.float64, device="cuda") if with_f else None
+        op.tracers_euler_step(dt, ud, out, f2)
+        torch.cuda.synchronize()
+        o = out.cpu().numpy()
+        assert np.array_equal(_bits(o[own]), _bits(want))
+        assert (o[ghost] == -777.0).all()                                       # ghost rows are left alone
+        if with_f:
+            assert np.array_equal(_bits(f2.cpu().numpy()), _bits(Fd))
+    assert np.array_equal(_bits(ud.cpu().numpy()), _bits(u))                    # not in place
+    with pytest.raises(RDyHipError) as e:
+        op.tracers_euler_step(dt, ud, ud)
+    assert e.value.code == 83
+    op.destroy()
+
+
+def test_primitive_variables_are_zeros_until_an_evaluation_follows_the_request():
+    torch = _torch()
+    case, ref, u, _ = _case("tri-270", 2, TRACER_RIEMANN_ROE)
+    mesh = case.mesh
+    op = _operator(case, ref, 2, TRACER_RIEMANN_ROE)
+    before = op.layout_info()["device_bytes"]
+    ud = _dev(u)
+    f = torch.empty((mesh.num_owned_cells, 5), dtype=torch.float64, device="cuda")
+    op.tracers_rhs_function(case.dt, ud, f)                    # before the request: stores nothing
+    pv = op.tracers_primitive_variables()
+    torch.cuda.synchronize()
+    assert pv.shape == (mesh.num_owned_cells, 5) and (pv.cpu().numpy() == 0.0).all()
+    assert op.layout_info()["device_bytes"] == before + 8 * 5 * mesh.num_owned_cells
+    op.tracers_euler_step(case.dt, ud, torch.empty_like(ud))   # either evaluation stores
+    torch.cuda.synchronize()
+    assert rel_linf(pv.cpu().numpy(), ref.primitive_variables) <= TOL
+    assert op.tracers_primitive_variables().data_ptr() == pv.data_ptr()
+    assert op.layout_info()["device_bytes"] == before + 8 * 5 * mesh.num_owned_cells
+    op.destroy()
+
+
+def test_enable_allocates_zeroed_arrays_and_counts_them():
+    case, ref, u, _ = _case("tri-30", 2, TRACER_RIEMANN_ROE)
+    mesh = case.mesh
+    op = CS.create_operator(case)
+    assert op.tracers_info() == (0, 0)
+    before = op.layout_info()["device_bytes"]
+    op.enable_tracers(2)
+    K = sum(b.num_edges for b in mesh.boundaries)
+    assert op.layout_info()["device_bytes"] == before + 8 * (2 * 5 * K + 2 * mesh.num_owned_cells)
+    for b, bnd in enumerate(mesh.boundaries):
+        assert (op.tracers_boundary_fluxes(b) == 0.0).all()
+    op.destroy()
+
+
+def test_refusals(rdyhip_kernel):
+    _torch()
+    lib = _lib.load()
+    mesh = _mesh("tri-30")
+    rng = np.random.default_rng(5)
+    # a critical-outflow boundary
+    outflow = random_case(rng, mesh, RDyFlowConfig())
+    assert M.CONDITION_CRITICAL_OUTFLOW in outflow.condition_types
+    op = CS.create_operator(outflow)
+    with pytest.raises(RDyHipError) as e:
+        op.enable_tracers(2)
+    assert e.value.code == 83 and "CRITICAL_OUTFLOW" in e.value.message and op.tracers_info() == (0, 0)
+    # not enabled: every other call refuses
+    with pytest.raises(RDyHipError) as e:
+        op.tracers_set_source(0, np.zeros(mesh.num_owned_cells))
+    assert e.value.code == 83 and "not enabled" in e.value.message
+    op.destroy()
+    # hydrostatic reconstruction, second order, XQ2018 (the first two exist in the tiled form only: RDYHIP_KERNEL=cell refuses at create)
+    pmesh = M.structured_tri_mesh(5, 3, 1.0, zfunc=_bathymetry, project_2d=True)
+    for cfg, m in ((RDyFlowConfig(well_balancing=WELL_BALANCING_HR), pmesh), (RDyFlowConfig(second_order=True), mesh),
+                   (RDyFlowConfig(source_method=SOURCE_IMPLICIT_XQ2018), mesh)):
+        try:
+            op = Operator.create(cfg, m)
+        except RDyHipError as err:
+            assert rdyhip_kernel == "cell" and err.code == 83 and cfg.source_method != SOURCE_IMPLICIT_XQ2018
+            continue
+        with pytest.raises(RDyHipError) as e:
+            op.enable_tracers(1)
+        assert e.value.code == 83 and op.tracers_info() == (0, 0)
+        op.destroy()
+    # NT = 0 and 8, an unknown solver, a second enable
+    case, ref, u, _ = _case("tri-30", 2, TRACER_RIEMANN_ROE)
+    op = CS.create_operator(case)
+    for n, r in ((0, 0), (8, 0), (-1, 0), (2, 2), (2, -1)):
+        with pytest.raises(RDyHipError) as e:
+            op.enable_tracers(n, r)
+        assert e.value.code == 83 and op.tracers_info() == (0, 0)
+    op.enable_tracers(2, TRACER_RIEMANN_UPWIND_ROE)
+    with pytest.raises(RDyHipError) as e:
+        op.enable_tracers(2, TRACER_RIEMANN_UPWIND_ROE)
+    assert e.value.code == 83 and op.tracers_info() == (2, TRACER_RIEMANN_UPWIND_ROE)
+    # a wrong num_edges, a boundary and a tracer index out of range, null arrays
+    b = next(i for i, bnd in enumerate(mesh.boundaries) if bnd.num_edges)
+    ne = mesh.boundaries[b].num_edges
+    vals = np.zeros((ne + 1, 5))
+    vp = vals.ctypes.data_as(_lib.c_double_p)
+    assert lib.rdyhip_tracers_set_boundary_values(op._h, b, ne + 1, vp) == 83
+    assert lib.rdyhip_tracers_get_boundary_fluxes(op._h, b, ne - 1, vp) == 83
+    assert lib.rdyhip_tracers_set_boundary_values(op._h, len(mesh.boundaries), ne, vp) == 83
+    assert lib.rdyhip_tracers_set_boundary_values(op._h, b, ne, None) == 83
+    assert lib.rdyhip_tracers_get_boundary_fluxes(op._h, b, ne, None) == 83
+    assert lib.rdyhip_tracers_set_source(op._h, 2, 1, None, vp) == 83 and lib.rdyhip_tracers_set_source(op._h, -1, 1, None, vp) == 83
+    assert lib.rdyhip_tracers_set_source(op._h, 0, 1, None, None) == 83
+    assert lib.rdyhip_tracers_rhs_function(op._h, 0.1, None, None, None) == 83
+    assert lib.rdyhip_tracers_euler_step(op._h, 0.1, None, None, None, None) == 83
+    assert lib.rdyhip_tracers_primitive_variables(op._h, None, None) == 83
+    op.destroy()
+
+
+def test_a_rank_that_owns_nothing():
+    torch = _torch()
+    mesh = _empty_mesh()
+    op = Operator.create(RDyFlowConfig(), mesh)
+    op.enable_tracers(3)
+    u = torch.zeros((mesh.num_cells, 6), dtype=torch.float64, device="cuda")
+    f = torch.empty((0, 6), dtype=torch.float64, device="cuda")
+    op.tracers_rhs_function(0.1, u, f)
+    out = torch.full_like(u, 5.0)
+    op.tracers_euler_step(0.1, u, out)
+    torch.cuda.synchronize()
+    assert (out.cpu().numpy() == 5.0).all()
+    assert op.tracers_primitive_variables().shape == (0, 6)
+    op.update_diagnostics()
+    assert op.get_diagnostics().max_courant_num == 0.0
+    op.destroy()
+
+
+@pytest.mark.parametrize("name", ["tri-270", "part-o2l"])
+def test_the_swe_path_is_undisturbed(name):
+    """After enable_tracers -- and a tracer evaluation -- rdyhip_rhs_function on a [num_cells, 3] state gives the bits of a fresh
+    operator without tracers: F, primitive variables, boundary fluxes and the Courant struct."""
+    torch = _torch()
+    case, ref, u, _ = _case(name, 2, TRACER_RIEMANN_ROE)
+    mesh = case.mesh
+    plain = CS.create_operator(case)
+    op = _operator(case, ref, 2, TRACER_RIEMANN_ROE)
+    op.tracers_primitive_variables()
+    op.tracers_rhs_function(case.dt, _dev(u), torch.empty((mesh.num_owned_cells, 5), dtype=torch.float64, device="cuda"))
+    u3 = _dev(case.u_local)
+    res = []
+    for o in (plain, op):
+        pv = o.primitive_variables
+        f = torch.full((mesh.num_owned_cells, 3), float("nan"), dtype=torch.float64, device="cuda")
+        o.rhs_function(case.dt, u3, f)
+        torch.cuda.synchronize()
+        o.update_diagnostics()
+        d = o.get_diagnostics()
+        res.append((f.cpu().numpy(), pv.cpu().numpy(), [o.boundary_fluxes(b) for b in range(len(mesh.boundaries))],
+                    [o.boundary_fluxes(b, accumulated=True) for b in range(len(mesh.boundaries))],
+                    (d.max_courant_num, d.global_edge_id, d.global_cell_id)))
+    a, b = res
+    assert np.isfinite(a[0]).all() and np.array_equal(_bits(a[0]), _bits(b[0])) and np.array_equal(_bits(a[1]), _bits(b[1]))
+    for x, y in zip(a[2] + a[3], b[2] + b[3]):
+        assert np.array_equal(_bits(x), _bits(y))
+    assert a[4] == b[4] and a[4][0] > 0.0
+    plain.destroy()
+    op.destroy()
+
+
+@pytest.mark.parametrize("riemann", [TRACER_RIEMANN_ROE, TRACER_RIEMANN_UPWIND_ROE])
+def test_sediment_mms_trajectory(riemann):
+    """40 Euler steps of the reference's sediment MMS case (two classes) at the base refinement level, every step through
+    rdyhip_tracers_euler_step with the sources and Dirichlet values of its half time, against the same loop in numpy"""
+    torch = _torch()
+
+    def make_apply(mesh):
+        op = Operator.create(RDyFlowConfig(), mesh, [M.CONDITION_DIRICHLET])
+        op.enable_tracers(2, riemann)
+        c = mesh.cell_centroids
+        import mms
+        op.set_domain_mannings_n(mms.fields(c[:, 0], c[:, 1], 0.0)["n"])
+
+        def apply(dt, u, src, tsrc, bvals):
+            for k in range(3):
+                op.set_domain_external_source(k, src[:, k])
+            for j in range(2):
+                op.tracers_set_source(j, tsrc[:, j])
+            op.tracers_set_boundary_values(0, bvals)
+            out = torch.empty((mesh.num_cells, 5), dtype=torch.float64, device="cuda")
+            op.tracers_euler_step(dt, _dev(u), out)
+            return out.cpu().numpy()
+        return apply
+
+    n, _, _, _, got = sediment_run_level(1, make_apply, nsteps=40)
+    _, _, _, _, want = sediment_run_level(1, reference_make_apply(riemann), nsteps=40)
+    # relative to the state's own size (h ~ 0.005: helpers.rel_linf would measure against 1)
+    err = float(np.abs(got - want).max() / np.abs(want).max())
+    print(f"riemann={riemann}: {n} cells, 40 steps, state vs reference {err:.3e}")
+    assert np.isfinite(got).all() and err <= TOL
