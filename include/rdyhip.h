@@ -786,6 +786,55 @@ int rdyhip_tracers_euler_step(RDyHipOperator op, double dt, const double *u_loca
 int rdyhip_tracers_primitive_variables(RDyHipOperator op, const double **device_ptr, int64_t *num_values);
 int rdyhip_tracers_get_boundary_fluxes(RDyHipOperator op, int32_t boundary, int32_t num_edges, double *fluxes /* host [num_edges][3+NT] */);
 
+/* ---- ensembles: several simulations on one mesh, one launch per evaluation --------------------------------------------------------
+ * The reference's `ensemble:` section (docs/common/input.md:158-225, docs/developer/organization.md:373-395; the test deck
+ * driver/tests/swe_roe/ex2b-ensemble.yaml: two members, Manning 0.015 and 0.030): ConfigureEnsembleMember (src/ensemble.c:5-84)
+ * splits the communicator, and every member gets ranks, a mesh copy, an operator and a TS of its own.  Here ONE operator holds
+ * B members side by side and evaluates all of them in one launch (csrc/ensemble_kernels.h): a thread loads its cell's geometry once
+ * and walks the members with it.  Results are per member, exactly as if each member ran alone.
+ *
+ * State: u_local is device memory [B][num_cells][3], f_global [B][num_owned_cells][3], member-major on purpose: member m's slice
+ *   u_local + 3 m num_cells is an ordinary SWE state, and every existing call works on it unchanged -- rdyhip_halo_exchange,
+ *   rdyhip_pack_cells, rdyhip_state_planes / rdyhip_state_read_*, rdyhip_error_sums, the output means.
+ * rdyhip_ensemble_enable: allocates per member Manning's n [B][owned], the external source [B][owned][3], boundary values and
+ *   boundary fluxes [B][K][3] each, the Courant buckets [B][W] (W = 4 x the workgroups of the cell-centric launch: 12 bytes each)
+ *   and the B 16-byte diagnostics -- B (32 owned + 48 K + 12 W + 16) bytes, counted in RDyHipLayoutInfo.device_bytes and freed by
+ *   rdyhip_destroy -- and fills every member's Manning's n, source and boundary values with the operator's current arrays by
+ *   device copies: a member then overrides only what differs (the rule of ConfigureEnsembleMember).  Boundary fluxes start at
+ *   zero.  It may synchronise.  rdyhip_ensemble_info: the number of members, 0: not enabled.
+ * rdyhip_ensemble_set_mannings / _set_external_source / _set_boundary_values: member `member`'s values, with the arguments of
+ *   rdyhip_set_mannings, rdyhip_set_external_source and rdyhip_set_boundary_values (all three components).  They synchronise.
+ * dts: one dt per member (each member has its own TS); dt enters the friction term and the Courant number.  The host array [B] is
+ *   read at the call and travels by value in the kernel arguments; neither evaluation call synchronises or copies.
+ * rdyhip_ensemble_rhs_function: for each member F is overwritten and never read, its boundary fluxes are stored and its diagnostic
+ *   starts anew; one launch serves all members.  RDYHIP_PHASE_ALL only, no accumulate form.
+ * rdyhip_ensemble_euler_step: u_local_out[m][owned rows] = fma(dts[m], F, u_local), not in place (u_local_out == u_local is
+ *   RDYHIP_ERR_USER); the ghost rows of u_local_out are left alone; with f_global == NULL F is never stored.
+ * rdyhip_ensemble_update_diagnostics: one merge launch for all members, one copy of B x 16 bytes, one stream synchronise;
+ *   rdyhip_ensemble_get_diagnostics then returns each member's value and ids, translated as rdyhip_update_diagnostics does.  Of
+ *   edges that tie, the first in the reference's loop order wins.
+ * Supported: first order, well_balancing NONE, both source methods, all three boundary types, triangles, quads and mixed meshes,
+ *   ranks with ghost cells.
+ * Stated differences: there is no accumulated boundary-flux array.  Primitive variables and the flux divergence are not stored.
+ *   The flux of a boundary edge is stored where its left cell is owned; rows of edges behind ghost cells are left as they are.  On
+ *   a rank with ghost cells the Courant diagnostic covers the edges of the owned cells with len / area_self only.  The SWE entry
+ *   points of an operator with the ensemble enabled behave exactly as before and share no array with it.
+ * Every argument error -- a null operator, num_members outside 1..RDYHIP_MAX_ENSEMBLE_MEMBERS, an operator created with
+ *   second_order or hydrostatic reconstruction, a second enable, any other call before enable, a member, boundary or component
+ *   index out of range, num_edges not the boundary's, a null array where one is needed -- is RDYHIP_ERR_USER and is reported
+ *   before any device call.  A rank that owns nothing launches nothing and succeeds. */
+#define RDYHIP_MAX_ENSEMBLE_MEMBERS 64
+int rdyhip_ensemble_enable(RDyHipOperator op, int32_t num_members);
+int rdyhip_ensemble_info(RDyHipOperator op, int32_t *num_members);                 /* 0: not enabled */
+int rdyhip_ensemble_set_mannings(RDyHipOperator op, int32_t member, int32_t n, const int32_t *owned_cell_ids /* NULL: 0..n-1 */, const double *values /* host */);
+int rdyhip_ensemble_set_external_source(RDyHipOperator op, int32_t member, int32_t comp, int32_t n, const int32_t *owned_cell_ids, const double *values);
+int rdyhip_ensemble_set_boundary_values(RDyHipOperator op, int32_t member, int32_t boundary, int32_t num_edges, const double *values /* host [num_edges][3] */);
+int rdyhip_ensemble_rhs_function(RDyHipOperator op, const double *dts /* host [B] */, const double *u_local, double *f_global, void *stream);
+int rdyhip_ensemble_euler_step(RDyHipOperator op, const double *dts, const double *u_local, double *u_local_out, double *f_global /* may be NULL */, void *stream);
+int rdyhip_ensemble_get_boundary_fluxes(RDyHipOperator op, int32_t member, int32_t boundary, int32_t num_edges, double *fluxes /* host [num_edges][3] */);
+int rdyhip_ensemble_update_diagnostics(RDyHipOperator op, void *stream);
+int rdyhip_ensemble_get_diagnostics(RDyHipOperator op, RDyHipCourant *courant /* [B] */);
+
 /* ---- introspection ----------------------------------------------------------
  * numbers describing the device layout, for DESIGN.md / bench.py */
 typedef struct {

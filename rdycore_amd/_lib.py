@@ -136,6 +136,16 @@ SYMBOLS = {
     "rdyhip_tracers_euler_step": (C.c_int, [_H, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rdyhip_tracers_primitive_variables": (C.c_int, [_H, C.POINTER(C.c_void_p), c_int64_p]),
     "rdyhip_tracers_get_boundary_fluxes": (C.c_int, [_H, C.c_int32, C.c_int32, c_double_p]),
+    "rdyhip_ensemble_enable": (C.c_int, [_H, C.c_int32]),
+    "rdyhip_ensemble_info": (C.c_int, [_H, c_int32_p]),
+    "rdyhip_ensemble_set_mannings": (C.c_int, [_H, C.c_int32, C.c_int32, c_int32_p, c_double_p]),
+    "rdyhip_ensemble_set_external_source": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, c_int32_p, c_double_p]),
+    "rdyhip_ensemble_set_boundary_values": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, c_double_p]),
+    "rdyhip_ensemble_rhs_function": (C.c_int, [_H, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rdyhip_ensemble_euler_step": (C.c_int, [_H, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rdyhip_ensemble_get_boundary_fluxes": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, c_double_p]),
+    "rdyhip_ensemble_update_diagnostics": (C.c_int, [_H, C.c_void_p]),
+    "rdyhip_ensemble_get_diagnostics": (C.c_int, [_H, C.POINTER(RDyHipCourant)]),
     "rdyhip_halo_create": (C.c_int, [_H, C.c_void_p, C.c_int32, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p, C.POINTER(C.c_void_p)]),
     "rdyhip_halo_destroy": (C.c_int, [C.POINTER(C.c_void_p)]),
     "rdyhip_halo_overlaps": (C.c_int32, [C.c_void_p]),

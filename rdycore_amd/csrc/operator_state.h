@@ -230,6 +230,14 @@ struct RDyHipOperator_s : LayoutCounts {
   DevBuf<double>       d_tr_bvalues, d_tr_bflux, d_tr_src, d_tr_pv;
   bool                 tr_pv_wanted = false;
   std::vector<int32_t> h_btype;    // [K] condition type of every boundary edge (the tracer path refuses critical outflow)
+  // rdyhip_ensemble_* (ensemble_kernels.h): B members on this operator's mesh, all allocated by rdyhip_ensemble_enable.  The
+  // launch is (grid, ens_groups) workgroups, every group walking ens_per_group members (the last one maybe fewer).
+  int32_t                    ens_members = 0, ens_groups = 0, ens_per_group = 0;   // 0 members: not enabled
+  DevBuf<double>             d_ens_mannings, d_ens_extsrc, d_ens_bvalues, d_ens_bflux;   // [B][owned], [B][owned][3], [B][K][3] x 2
+  DevBuf<double>             d_ens_blk_max;   // [B][ENSEMBLE_WAVES * grid] one Courant bucket per member and wave
+  DevBuf<int32_t>            d_ens_blk_pos;
+  DevBuf<DeviceCourant>      d_ens_courant;   // [B]
+  std::vector<RDyHipCourant> ens_courant;     // [B] what rdyhip_ensemble_update_diagnostics read last
 
   int64_t device_bytes = 0;
 };

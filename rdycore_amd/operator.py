@@ -484,6 +484,98 @@ class Operator:
         _lib.check(_lib.load().rdyhip_tracers_get_boundary_fluxes(self._h, int(boundary), n, out.ctypes.data_as(_lib.c_double_p) if out.size else None))
         return out
 
+    # -- ensembles (src/ensemble.c): B members on this mesh, state [B, num_cells, 3], one launch per evaluation ---------------------
+    num_members = 0
+
+    def enable_ensemble(self, num_members: int):
+        """rdyhip_ensemble_enable: `num_members` (1..64) members, each starting with the operator's current Manning's n, external
+        source and boundary values; a member then overrides only what differs"""
+        _lib.check(_lib.load().rdyhip_ensemble_enable(self._h, int(num_members)))
+        self.num_members = int(num_members)
+
+    def ensemble_info(self) -> int:
+        """rdyhip_ensemble_info: the number of members, 0: not enabled"""
+        n = C.c_int32()
+        _lib.check(_lib.load().rdyhip_ensemble_info(self._h, C.byref(n)))
+        return n.value
+
+    def _check_ensemble_state(self, t, name: str, cells: int, optional: bool = False):
+        if optional and t is None:
+            return
+        b = self.num_members
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == 3 * b * cells):
+            raise RDyHipError(83, f"{name} must be a contiguous float64 device tensor of {b} members x {cells} cells x 3")
+
+    def _ensemble_dts(self, dts):
+        d = np.ascontiguousarray(dts, dtype=np.float64).ravel()
+        if d.size != self.num_members:
+            raise RDyHipError(83, f"dts must hold one dt per member ({self.num_members}), not {d.size}")
+        return d
+
+    @staticmethod
+    def _region(values, owned_cell_ids):
+        v = np.ascontiguousarray(values, dtype=np.float64).ravel()
+        ip, ids = None, None
+        if owned_cell_ids is not None:
+            ids = np.ascontiguousarray(owned_cell_ids, dtype=np.int32).ravel()
+            if ids.size != v.size:
+                raise RDyHipError(60, f"size ({v.size}) does not match the region size ({ids.size})")
+            ip = ids.ctypes.data_as(_lib.c_int32_p)
+        return v, ids, ip
+
+    def ensemble_set_mannings_n(self, member: int, values, owned_cell_ids=None):
+        """rdyhip_ensemble_set_mannings: member `member`'s Manning's n in the owned cells `owned_cell_ids` (None: cells 0 .. n - 1)"""
+        v, ids, ip = self._region(values, owned_cell_ids)
+        _lib.check(_lib.load().rdyhip_ensemble_set_mannings(self._h, int(member), int(v.size), ip, v.ctypes.data_as(_lib.c_double_p) if v.size else None))
+
+    def ensemble_set_external_source(self, member: int, comp: int, values, owned_cell_ids=None):
+        """rdyhip_ensemble_set_external_source: component `comp` of member `member`'s source"""
+        v, ids, ip = self._region(values, owned_cell_ids)
+        _lib.check(_lib.load().rdyhip_ensemble_set_external_source(self._h, int(member), int(comp), int(v.size), ip,
+                                                                   v.ctypes.data_as(_lib.c_double_p) if v.size else None))
+
+    def ensemble_set_boundary_values(self, member: int, boundary: int, values):
+        """values[e, :] = (h, hu, hv) of boundary edge e for member `member` (rdyhip_ensemble_set_boundary_values)"""
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        ne = v.shape[0] if v.ndim == 2 and v.shape[1] == 3 else -1
+        _lib.check(_lib.load().rdyhip_ensemble_set_boundary_values(self._h, int(member), int(boundary), int(ne),
+                                                                   v.ctypes.data_as(_lib.c_double_p) if v.size else None))
+
+    def ensemble_rhs_function(self, dts, u_local: torch.Tensor, f_global: torch.Tensor):
+        """rdyhip_ensemble_rhs_function: f_global [B, owned, 3] = F_m(u_local [B, num_cells, 3]) with dts[m], every member's
+        diagnostics reset, one launch"""
+        d = self._ensemble_dts(dts)
+        self._check_ensemble_state(u_local, "u_local", self.mesh.num_cells)
+        self._check_ensemble_state(f_global, "f_global", self.mesh.num_owned_cells)
+        _lib.check(_lib.load().rdyhip_ensemble_rhs_function(self._h, d.ctypes.data_as(_lib.c_double_p), _ptr(u_local), _ptr(f_global), _stream()))
+
+    def ensemble_euler_step(self, dts, u_local: torch.Tensor, u_out: torch.Tensor, f_global: Optional[torch.Tensor] = None):
+        """rdyhip_ensemble_euler_step: u_out[m, owned rows] = fma(dts[m], F_m, u_local), not in place; f_global=None: F is never stored"""
+        d = self._ensemble_dts(dts)
+        self._check_ensemble_state(u_local, "u_local", self.mesh.num_cells)
+        self._check_ensemble_state(u_out, "u_out", self.mesh.num_cells)
+        self._check_ensemble_state(f_global, "f_global", self.mesh.num_owned_cells, optional=True)
+        _lib.check(_lib.load().rdyhip_ensemble_euler_step(self._h, d.ctypes.data_as(_lib.c_double_p), _ptr(u_local), _ptr(u_out),
+                                                          _ptr(f_global) if f_global is not None else None, _stream()))
+
+    def ensemble_boundary_fluxes(self, member: int, boundary: int) -> np.ndarray:
+        """rdyhip_ensemble_get_boundary_fluxes: [num_edges, 3] fluxes of member `member` through the edges of `boundary` (rows of
+        edges whose left cell is a ghost are not written)"""
+        n = self.mesh.boundaries[boundary].num_edges if 0 <= boundary < len(self.mesh.boundaries) else 0
+        out = np.zeros((n, 3))
+        _lib.check(_lib.load().rdyhip_ensemble_get_boundary_fluxes(self._h, int(member), int(boundary), n,
+                                                                   out.ctypes.data_as(_lib.c_double_p) if out.size else None))
+        return out
+
+    def ensemble_update_diagnostics(self):
+        _lib.check(_lib.load().rdyhip_ensemble_update_diagnostics(self._h, _stream()))
+
+    def ensemble_get_diagnostics(self) -> list:
+        """rdyhip_ensemble_get_diagnostics: one CourantNumberDiagnostics per member"""
+        c = (_lib.RDyHipCourant * max(self.num_members, 1))()
+        _lib.check(_lib.load().rdyhip_ensemble_get_diagnostics(self._h, c))
+        return [CourantNumberDiagnostics(c[m].max_courant_num, c[m].global_edge_id, c[m].global_cell_id) for m in range(self.num_members)]
+
     # -- second order: ComputeLeastSquaresGradients for the owned cells (src/operator_fluxes_ceed.c:998-1042)
     def compute_gradients(self, u_local: torch.Tensor, phase: int = PHASE_ALL):
         _lib.check(_lib.load().rdyhip_compute_gradients(self._h, int(phase), _ptr(u_local), _stream()))

@@ -31,6 +31,7 @@ from __future__ import annotations
 import dataclasses
 from typing import Optional, Sequence
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -252,3 +253,40 @@ class EulerStepper:
             self.rhs(h, y, k[j])
         for j, b in enumerate((1.0 / 6.0, 1.0 / 3.0, 1.0 / 3.0, 1.0 / 6.0)):
             self.op.axpy_owned(b * h, k[j], u_local)
+
+
+class EnsembleEulerStepper:
+    """Forward Euler for an operator with the ensemble enabled (Operator.enable_ensemble): every member takes the same number of
+    steps, member m with its own fixed dts[m], one fused launch per step for all members (rdyhip_ensemble_euler_step), the
+    steps ping-ponging between two [B, num_cells, 3] arrays.  Adaptive per-member dt is a follow-up."""
+
+    def __init__(self, op):
+        self.op = op
+        self.step = 0
+        self.times = None        # [B] the time every member has reached
+        self._own = [None, None]  # the stepper's arrays: the partner of the caller's array, and the partner of that one
+
+    def _partner(self, u: torch.Tensor) -> torch.Tensor:
+        """the array the first step from `u` writes: the stepper's first array, or -- when `u` is one of the stepper's own, the
+        result of an earlier advance handed back -- its other one.  Never `u`, and never an array of the caller's."""
+        k = 1 if self._own[0] is u else 0
+        a = self._own[k]
+        if a is None or a.shape != u.shape or a.device != u.device:
+            a = self._own[k] = u.clone()     # ghost rows start as u's
+        return a
+
+    def advance(self, u: torch.Tensor, dts, nsteps: int) -> torch.Tensor:
+        """`nsteps` steps from `u`; returns the array that holds the result: `u` after an even number of steps, else one of the
+        stepper's own two arrays (a later advance overwrites it: copy what must be kept), which may be handed back as the next
+        `u`.  No array of the caller's other than `u` is written.  Ghost rows are the caller's: a rank with
+        ghost cells exchanges every member's slice of the returned array between calls."""
+        d = np.ascontiguousarray(dts, dtype=np.float64).ravel()
+        if self.times is None:
+            self.times = np.zeros(d.size)
+        cur, nxt = u, self._partner(u)
+        for _ in range(int(nsteps)):
+            self.op.ensemble_euler_step(d, cur, nxt)
+            cur, nxt = nxt, cur
+            self.times = self.times + d
+            self.step += 1
+        return cur
