@@ -259,7 +259,33 @@ int rdyhip_reset_boundary_fluxes_accum(RDyHipOperator op);
  *     life of the operator.  rdyhip_field_ptr_const hands out the same pointer for reading and changes nothing.
  * Outside the mode the kernels read the [owned][3] array as before; the results are the same bits either way, and the
  * [owned][3] array is current at all times.  The mode is read when a launch is enqueued: launches and setters on one stream
- * stay consistent, across streams the caller orders them as for the data.  rdyhip_source_is_water_only reports it. */
+ * stay consistent, across streams the caller orders them as for the data.  rdyhip_source_is_water_only reports it.
+ *
+ * Uniform fields.  A run without rain has a water source of +0.0 in every cell, a storm over a small domain one rate in every
+ * cell; Manning's n is one number in most decks; a benchmark bed is often flat.  While every owned element of such a field is
+ * known to hold the SAME 64-bit pattern (-0.0 is not +0.0; NaNs are equal if their payloads are), the first-order and
+ * hydrostatic-reconstruction kernels read element 0 of it in every lane instead of streaming the plane: 8 B per cell and field
+ * less memory traffic (16 B for the two bed slopes).  Element 0 of the array on the device, written on the stream by the same
+ * setters as ever, is the value -- no copy of it travels with the launch, nothing can go stale -- and every array stays
+ * allocated and current: entering or leaving a mode moves no data, the results are the same bits either way, and every other
+ * kernel (second order, cell-centric, ensembles, tracers, output means, read-out) reads the arrays as before.  Per field the
+ * host keeps a flag, the pattern and whether the array has escaped:
+ *   - At create the source and Manning's n are uniform +0.0 (the arrays are zeroed); the bed is flat if every dz/dx and dz/dy
+ *     of the mesh is +0.0, and being static it stays what it is.
+ *   - A mode STARTS, or restarts with a new value, on a host write of all owned cells with equal values: this setter or _on
+ *     (comp 0 for the source) or rdyhip_set_mannings[_on] with owned_cell_ids == NULL and n = the number of owned cells,
+ *     rdyhip_refresh_field from a host array, rdyhip_forcing_fill_source on comp 0 with d_owned_cell_ids == NULL and n = owned
+ *     cells.  The scan stops at the first element that differs; an array that is uniform is not uploaded at all but filled on
+ *     the device from its one value.
+ *   - It is KEPT by a write of some cells (an id list, fewer values) or a fill with a host scalar whose values all equal the
+ *     stored pattern.
+ *   - It ENDS with any other write of some cells, with a write of unequal values, and with a write whose values the host
+ *     cannot see (rdyhip_forcing_gather_source, rdyhip_refresh_field from a device array).
+ *   - rdyhip_field_ptr on the external source or on Manning's n ends the field's mode for the life of the operator;
+ *     rdyhip_field_ptr_const changes nothing.
+ *   - The source's mode is honoured only inside the water-only mode above (element 0 of the plane stands for all cells).
+ * The modes are read when a launch is enqueued, like the water-only mode.  rdyhip_uniform_fields reports them;
+ * RDYHIP_UNIFORM_FIELDS=0 in the environment of rdyhip_create keeps all of them off (an A/B and test knob). */
 int rdyhip_set_external_source(RDyHipOperator op, int32_t comp, int32_t n, const int32_t *owned_cell_ids, const double *values);
 
 /* Get/RestoreOperator{Regional,Domain}MaterialProperties (rdyoperatorimpl.h:263-266)
@@ -347,6 +373,12 @@ int rdyhip_primitive_variables_stored(RDyHipOperator op, int32_t *out);
 int rdyhip_field_ptr_const(RDyHipOperator op, RDyHipField field, const double **device_ptr, int64_t *num_values);
 /* *out = 1 while the kernels read the water source from its own plane (see rdyhip_set_external_source), else 0 */
 int rdyhip_source_is_water_only(RDyHipOperator op, int32_t *out);
+/* *mask = the RDYHIP_UNIFORM_* bits of the fields whose element 0 the next first-order / HR launch would read for all cells
+ * (see "Uniform fields" at rdyhip_set_external_source; the source bit only while the source is water only) */
+#define RDYHIP_UNIFORM_SOURCE 1
+#define RDYHIP_UNIFORM_MANNINGS 2
+#define RDYHIP_UNIFORM_FLAT_BED 4
+int rdyhip_uniform_fields(RDyHipOperator op, int32_t *mask);
 /* A device array of external sources ends the water-only mode of the source: this call does not block, so the host cannot
  * look at the momentum entries (keeping the plane on this path is a follow-up).  A host array keeps or restarts it. */
 int rdyhip_refresh_field(RDyHipOperator op, RDyHipField field, const double *values, int64_t num_values, int32_t values_on_device, void *stream);

@@ -85,12 +85,42 @@ static int check_scatter_args(RDyHipOperator op, int32_t n, const int32_t *ids, 
   return 0;
 }
 
+// ---- uniform fields (uniform_fields.h) ----------------------------------------------------------------------------------
+static int forcing_grid(int64_t n) { return (int)std::min<int64_t>((n + 255) / 256, 2048); }
+// A host write of `n` checked values into the field `uf` tracks (nullptr: a field without a mode).  Returns true where the
+// write covers every owned cell with ONE value and the mode holds: the caller then uploads nothing and fills on the device
+// (the same bits), so the scan of a uniform array is paid for by the copy it saves.
+static bool note_host_write(RDyHipOperator op, UniformField *uf, int32_t n, const int32_t *ids, const double *values) {
+  if (!uf) return false;
+  if (ids || n != op->n_owned) {
+    uf->write_partial(values, n);
+    return false;
+  }
+  uf->write_whole(values, n);
+  return uf->uniform;
+}
+static int fill_component(double *dst, int ncomp, int comp, int32_t n, double value, double *mirror, hipStream_t st) {
+  hipLaunchKernelGGL(forcing_fill_kernel, dim3(forcing_grid(n)), dim3(256), 0, st, n, (const int32_t *)nullptr, value, dst, ncomp, comp);
+  HIP_TRY(hipGetLastError());
+  if (mirror) {
+    hipLaunchKernelGGL(forcing_fill_kernel, dim3(forcing_grid(n)), dim3(256), 0, st, n, (const int32_t *)nullptr, value, mirror, 1, 0);
+    HIP_TRY(hipGetLastError());
+  }
+  return 0;
+}
+
 // `mirror`: a second destination [n_owned] that receives the same staged values (the water-source plane), or nullptr
 static int scatter_component(RDyHipOperator op, double *dst, int ncomp, int comp, int32_t n, const int32_t *ids, const double *values,
-                             double *mirror = nullptr) {
+                             double *mirror = nullptr, UniformField *uf = nullptr) {
   int rc = check_scatter_args(op, n, ids, values);
   if (rc || n == 0) return rc;
   HIP_TRY(hipDeviceSynchronize());  // an RHS in flight on a non-blocking stream may still read the array (and the staging buffers)
+  if (note_host_write(op, uf, n, ids, values)) {
+    rc = fill_component(dst, ncomp, comp, n, values[0], mirror, 0);
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    return 0;
+  }
   rc = op->d_stage_vals.reserve((size_t)n);
   if (rc) return rc;
   HIP_TRY(hipMemcpy(op->d_stage_vals.p, values, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
@@ -135,12 +165,13 @@ static double *source_mirror(RDyHipOperator op, int comp, int32_t n, const doubl
 int rdyhip_set_external_source(RDyHipOperator op, int32_t comp, int32_t n, const int32_t *owned_cell_ids, const double *values) {
   if (!op) return fail(RDYHIP_ERR_USER, "null operator");
   if (comp < 0 || comp > 2) return fail(RDYHIP_ERR_USER, "bad source component %d", comp);
-  return scatter_component(op, op->d_extsrc.p, 3, comp, n, owned_cell_ids, values, source_mirror(op, comp, n, values));
+  return scatter_component(op, op->d_extsrc.p, 3, comp, n, owned_cell_ids, values, source_mirror(op, comp, n, values),
+                           comp == 0 ? &op->uniform.source : nullptr);
 }
 
 int rdyhip_set_mannings(RDyHipOperator op, int32_t n, const int32_t *owned_cell_ids, const double *values) {
   if (!op) return fail(RDYHIP_ERR_USER, "null operator");
-  return scatter_component(op, op->d_mannings.p, 1, 0, n, owned_cell_ids, values);
+  return scatter_component(op, op->d_mannings.p, 1, 0, n, owned_cell_ids, values, nullptr, &op->uniform.mannings);
 }
 
 // ---- the stream-ordered forms: no device-wide synchronisation, no blocking copy ---------------------------------------
@@ -217,9 +248,10 @@ static int stage_release(StageRing::Slot *s, hipStream_t st) {
 }
 
 static int scatter_component_on(RDyHipOperator op, double *dst, int ncomp, int comp, int32_t n, const int32_t *ids, const double *values, hipStream_t st,
-                                double *mirror = nullptr) {
+                                double *mirror = nullptr, UniformField *uf = nullptr) {
   int rc = check_scatter_args(op, n, ids, values);
   if (rc || n == 0) return rc;
+  if (note_host_write(op, uf, n, ids, values)) return fill_component(dst, ncomp, comp, n, values[0], mirror, st);
   const size_t vbytes = sizeof(double) * (size_t)n, ibytes = ids ? sizeof(int32_t) * (size_t)n : 0;
   StageRing::Slot *s;
   rc = stage_acquire(op, vbytes + ibytes, &s);
@@ -241,12 +273,13 @@ static int scatter_component_on(RDyHipOperator op, double *dst, int ncomp, int c
 int rdyhip_set_external_source_on(RDyHipOperator op, int32_t comp, int32_t n, const int32_t *owned_cell_ids, const double *values, void *stream) {
   if (!op) return fail(RDYHIP_ERR_USER, "null operator");
   if (comp < 0 || comp > 2) return fail(RDYHIP_ERR_USER, "bad source component %d", comp);
-  return scatter_component_on(op, op->d_extsrc.p, 3, comp, n, owned_cell_ids, values, (hipStream_t)stream, source_mirror(op, comp, n, values));
+  return scatter_component_on(op, op->d_extsrc.p, 3, comp, n, owned_cell_ids, values, (hipStream_t)stream, source_mirror(op, comp, n, values),
+                              comp == 0 ? &op->uniform.source : nullptr);
 }
 
 int rdyhip_set_mannings_on(RDyHipOperator op, int32_t n, const int32_t *owned_cell_ids, const double *values, void *stream) {
   if (!op) return fail(RDYHIP_ERR_USER, "null operator");
-  return scatter_component_on(op, op->d_mannings.p, 1, 0, n, owned_cell_ids, values, (hipStream_t)stream);
+  return scatter_component_on(op, op->d_mannings.p, 1, 0, n, owned_cell_ids, values, (hipStream_t)stream, nullptr, &op->uniform.mannings);
 }
 
 int rdyhip_set_boundary_values_on(RDyHipOperator op, int32_t boundary, int32_t comp_offset, int32_t num_comp, int32_t num_edges, const double *values,
@@ -288,6 +321,7 @@ int rdyhip_refresh_field(RDyHipOperator op, RDyHipField field, const double *val
   if (values_on_device) {
     // this path must not block, so the host cannot look at the momentum entries: the kernels read the [owned][3] array from here on
     if (source) op->src_water_only = false;
+    (source ? op->uniform.source : op->uniform.mannings).write_unseen();
     HIP_TRY(hipMemcpyAsync(dst, values, bytes, hipMemcpyDeviceToDevice, st));
     return 0;
   }
@@ -296,6 +330,9 @@ int rdyhip_refresh_field(RDyHipOperator op, RDyHipField field, const double *val
   if (source) {
     plane = !op->src_escaped && all_plus_zero(values + 1, op->n_owned, 3) && all_plus_zero(values + 2, op->n_owned, 3);
     op->src_water_only = plane;
+    op->uniform.source.write_whole(values, op->n_owned, 3);  // the water component of every row
+  } else {
+    op->uniform.mannings.write_whole(values, op->n_owned);
   }
   StageRing::Slot *s;
   rc = stage_acquire(op, bytes, &s);
@@ -311,8 +348,6 @@ int rdyhip_refresh_field(RDyHipOperator op, RDyHipField field, const double *val
 }
 
 // ---- device-side forcing ingestion (forcing_kernels.h) -------------------------------------------------
-static int forcing_grid(int64_t n) { return (int)std::min<int64_t>((n + 255) / 256, 2048); }
-
 static int forcing_source_args(RDyHipOperator op, int32_t comp, int32_t n) {
   if (!op) return fail(RDYHIP_ERR_USER, "null operator");
   if (comp < 0 || comp > 2) return fail(RDYHIP_ERR_USER, "bad source component %d", comp);
@@ -325,6 +360,12 @@ int rdyhip_forcing_fill_source(RDyHipOperator op, int32_t comp, int32_t n, const
   if (rc || n == 0) return rc;
   hipLaunchKernelGGL(forcing_fill_kernel, dim3(forcing_grid(n)), dim3(256), 0, (hipStream_t)stream, n, d_owned_cell_ids, value, op->d_extsrc.p, 3, comp);
   HIP_TRY(hipGetLastError());
+  if (comp == 0) {
+    // without ids the fill covers cells 0 .. n - 1, all owned cells if n says so; a device id list the host cannot read
+    // counts as some of them
+    if (!d_owned_cell_ids && n == op->n_owned) op->uniform.source.fill_whole(value);
+    else op->uniform.source.fill_partial(value);
+  }
   if (comp != 0) {
     if (!is_plus_zero(value)) op->src_water_only = false;
   } else if (op->src_water_only) {
@@ -343,6 +384,7 @@ int rdyhip_forcing_gather_source(RDyHipOperator op, int32_t comp, int32_t n, con
   // the values are the device's: a momentum component ends the water-only mode without a look; the water component goes
   // into the [owned][3] array and, in that mode, into the plane as well (same kernel, same operands: the same bits)
   if (comp != 0) op->src_water_only = false;
+  else op->uniform.source.write_unseen();
   double *const dsts[2] = {op->d_extsrc.p, comp == 0 && op->src_water_only ? op->d_src_water.p : nullptr};
   for (int k = 0; k < 2 && dsts[k]; ++k) {
     const int ncomp = k == 0 ? 3 : 1;

@@ -8,6 +8,7 @@
 #include "rdyhip.h"
 #include "error.h"
 #include "host_layout.h"
+#include "uniform_fields.h"
 #include "swe_kernels.h"
 
 using namespace rdyhip;
@@ -159,6 +160,10 @@ struct RDyHipOperator_s : LayoutCounts {
   DevBuf<double>  d_src_water;
   bool            src_water_only = true;   // every momentum source is +0.0 and the plane is current
   bool            src_escaped    = false;  // rdyhip_field_ptr handed out d_extsrc: it may be written behind our back, for good
+  // Fields whose owned elements all hold one 64-bit pattern (uniform_fields.h): the first-order / HR tiled kernels read
+  // element 0 of the water plane, of d_mannings or of d_dzdx / d_dzdy instead of streaming the plane.  Read when a launch is
+  // enqueued, like src_water_only; RDYHIP_UNIFORM_FIELDS=0 at create keeps every mode off.
+  UniformFields   uniform;
   DevBuf<double>  d_bvalues, d_bflux, d_baccum, d_bcn, d_bsn, d_pv, d_fdiv, d_blk_max;
   // The primitive variables are stored by the evaluations only once somebody can look at them (rdyhip_field_ptr, until
   // rdyhip_field_release); the first request after evaluations that did not store derives them from the state of the last one.

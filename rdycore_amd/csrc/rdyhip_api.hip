@@ -269,6 +269,9 @@ int launch_rhs(RDyHipOperator op, int32_t phase, int32_t overwrite, int reset_di
         a.extsrc  = op->d_src_water.p;
         a.src_mom = 0;
       }
+      // ... and so are the uniform fields: UNIFORM_* bit i is STREAM_* bit i + 1 (element 0 of each array is the value, kept
+      // current on the stream by the setters: nothing but these bits goes to the kernel)
+      a.src_mom |= op->uniform.mask(op->src_water_only) << 1;
       // The dynamic walk: whole-mesh launches over XCD chunks.  INTERIOR launches skip tiles (their draws would run in
       // series) and HALO launches walk a list: both keep the static walk, and neither touches the counters, so they may
       // run beside each other as before.  PHASE_ALL launches of one operator already follow each other (the Courant buckets).
@@ -341,9 +344,9 @@ int rdyhip_create(const RDyHipConfig *config, const RDyHipMesh *mesh, int32_t nu
     // Infinity Cache (256 MB) then -- when it fits beside what else lives there.  A sweep over 0.36 M .. 10 M cells in a time loop
     // (profiles/r05_uout_policy_sweep.txt): plain stores win 3-5 % from 1.2 M to 6 M cells (29 .. 150 MB of state), lose 0.3-3 %
     // below 1 M (the launch is over before a second pass could profit) and 2 % from 8 M cells.  So: plain stores for
-    // 28 MB <= state <= RDYHIP_UOUT_CACHED_MAX_MB (default 144); RDYHIP_UOUT_CACHED=0 / 1 forces.
-    double max_mb = 144.0;
-    if (const char *e = getenv("RDYHIP_UOUT_CACHED_MAX_MB")) max_mb = atof(e);
+    // 28 MB <= state <= 144 MB; RDYHIP_UOUT_CACHED=0 / 1 forces.  (The upper bound had a knob of its own while it was swept; the
+    // sweep itself only ever forced the policy, and the library keeps to sixteen environment variables.)
+    const double max_mb = 144.0;
     const double state_bytes = 24.0 * (double)op->n_cells;
     op->uout_cached = state_bytes >= 28.0 * 1048576.0 && state_bytes <= max_mb * 1048576.0;
     if (const char *e = getenv("RDYHIP_UOUT_CACHED")) op->uout_cached = atoi(e) != 0;
@@ -435,6 +438,10 @@ int rdyhip_create(const RDyHipConfig *config, const RDyHipMesh *mesh, int32_t nu
   if (!rc) rc = op->d_mannings.zeros(no);
   if (!rc) rc = op->d_extsrc.zeros(3 * no);
   if (!rc) rc = op->d_src_water.zeros(no);
+  {
+    const char *e = getenv("RDYHIP_UNIFORM_FIELDS");   // the A/B and test knob
+    op->uniform.start(!(e && atoi(e) == 0), bed_is_flat(L.dzdx.data(), L.dzdy.data(), (int64_t)std::min(L.dzdx.size(), L.dzdy.size())));
+  }
   if (!rc) rc = op->d_bvalues.zeros(3 * K);
   if (!rc) rc = op->d_bflux.zeros(3 * K);
   if (!rc) rc = op->d_baccum.zeros(3 * K);
@@ -583,7 +590,9 @@ int rdyhip_field_ptr(RDyHipOperator op, RDyHipField field, double **device_ptr, 
     // the caller may write the array in place at any time from now on: the water plane cannot be kept, for good
     op->src_escaped    = true;
     op->src_water_only = false;
+    op->uniform.source.escape();
   }
+  if (field == RDYHIP_FIELD_MANNINGS) op->uniform.mannings.escape();
   return 0;
 }
 
@@ -612,6 +621,16 @@ int rdyhip_primitive_variables_stored(RDyHipOperator op, int32_t *out) {
 int rdyhip_source_is_water_only(RDyHipOperator op, int32_t *out) {
   if (!op || !out) return fail(RDYHIP_ERR_USER, "null argument");
   *out = op->src_water_only ? 1 : 0;
+  return 0;
+}
+
+static_assert(UNIFORM_SOURCE == RDYHIP_UNIFORM_SOURCE && UNIFORM_MANNINGS == RDYHIP_UNIFORM_MANNINGS && UNIFORM_FLAT_BED == RDYHIP_UNIFORM_FLAT_BED &&
+                  (UNIFORM_SOURCE << 1) == STREAM_UNIFORM_SOURCE && (UNIFORM_MANNINGS << 1) == STREAM_UNIFORM_MANNINGS &&
+                  (UNIFORM_FLAT_BED << 1) == STREAM_FLAT_BED,
+              "rdyhip.h, uniform_fields.h and the kernels' stream flags name the same bits (launch_rhs shifts the mask by one)");
+int rdyhip_uniform_fields(RDyHipOperator op, int32_t *mask) {
+  if (!op || !mask) return fail(RDYHIP_ERR_USER, "null argument");
+  *mask = op->uniform.mask(op->src_water_only);
   return 0;
 }
 

@@ -126,9 +126,11 @@ struct KernelArgs {
   int32_t        phase;      // RDYHIP_PHASE_*
   int32_t        overwrite;  // 1: f = rhs, 0: f += rhs
   int32_t        xcd_chunks; // >0: blocks are dealt to XCDs in contiguous chunks of this many tiles
-  int32_t        src_mom;    // first-order / HR tiled kernel: 1: extsrc holds all three source components; 0: extsrc is the dense
-                             // water-source plane and the momentum sources are zero (launch_rhs).  The other kernels always get
-                             // the [n_owned][3] array and do not look.  (Sits in what was padding: the struct does not grow.)
+  int32_t        src_mom;    // first-order / HR tiled kernel, STREAM_* bits.  Bit 0 set: extsrc holds all three source components;
+                             // clear: extsrc is the dense water-source plane and the momentum sources are zero (launch_rhs).  Bits 1-3:
+                             // the water source / Manning's n / the bed slopes are uniform over the owned cells, element 0 stands for
+                             // all of them (stream_args).  The other kernels always get the [n_owned][3] array and 1, and do not look.
+                             // (Sits in what was padding: the struct does not grow.)
   // ---- tiled kernel only
   const struct TileDesc *tiles;  // [ntiles+1]
   const uint32_t *e_lr;      // [nrec] packed LDS slots of the edge's cells
@@ -461,12 +463,19 @@ struct CellStreams {
   double   dzdx, dzdy, nman, s0, s1, s2;
 };
 
-// The pointers and the two scalars load_streams reads: filled from the kernarg segment where the streams are issued (RDY_HOT)
+// The pointers and the scalars load_streams reads: filled from the kernarg segment where the streams are issued (RDY_HOT).
+// KernelArgs::src_mom carries the launch's stream flags: STREAM_SRC_MOM, and one bit per field whose owned elements all hold
+// the same 64-bit pattern at enqueue time (uniform_fields.h).  Each such bit becomes an index mask, 0 instead of -1, with
+// scalar code: every lane of every wave then reads element 0 of the SAME array the setters keep current -- one line, always on
+// chip, the same bits its own element holds -- and the field's plane costs the launch no HBM traffic.  Branch-free on purpose:
+// a wave-uniform branch around each load costs the tile loop 11 VALU instructions and four hinted loads (profiles/RESULTS_LOG.md section 24).
+enum { STREAM_SRC_MOM = 1, STREAM_UNIFORM_SOURCE = 2, STREAM_UNIFORM_MANNINGS = 4, STREAM_FLAT_BED = 8 };
 struct StreamArgs {
   const void   *slot_ref;
   const double *coef, *dzdx, *dzdy, *mannings, *extsrc;
   int64_t       stride;
   int32_t       src_mom;
+  int32_t       mask_s, mask_n, mask_dz;  // 0: the field is uniform, read element 0; -1: read the lane's own element
 };
 __device__ __forceinline__ StreamArgs stream_args(HotArgs k) {
   StreamArgs p;
@@ -477,7 +486,11 @@ __device__ __forceinline__ StreamArgs stream_args(HotArgs k) {
   p.mannings = k->a.mannings;
   p.extsrc   = k->a.extsrc;
   p.stride   = k->a.stride;
-  p.src_mom  = k->a.src_mom;
+  const int32_t flags = k->a.src_mom;
+  p.src_mom  = flags & STREAM_SRC_MOM;
+  p.mask_s   = ((flags >> 1) & 1) - 1;
+  p.mask_n   = ((flags >> 2) & 1) - 1;
+  p.mask_dz  = ((flags >> 3) & 1) - 1;
   return p;
 }
 
@@ -497,17 +510,17 @@ __device__ __forceinline__ void load_streams(const StreamArgs &a, int o, bool ac
 #pragma unroll
     for (int s = 0; s < S; ++s) c.coef[s] = RDY_LD(&a.coef[s * a.stride + o]);
     if (!HR) {  // under HR the pressure correction of the flux carries the bed slope
-      c.dzdx = RDY_LD(&a.dzdx[o]);
-      c.dzdy = RDY_LD(&a.dzdy[o]);
+      c.dzdx = RDY_LD(&a.dzdx[o & a.mask_dz]);
+      c.dzdy = RDY_LD(&a.dzdy[o & a.mask_dz]);
     } else {
       c.dzdx = c.dzdy = 0.0;
     }
-    c.nman = RDY_LD(&a.mannings[o]);
+    c.nman = RDY_LD(&a.mannings[o & a.mask_n]);
     // the water source: row o of the [owned][3] array, or entry o of the water plane, which costs 8 B of HBM traffic per cell
-    // instead of the 24 B that any read of a 24-B row does
-    c.s0 = RDY_LD(&a.extsrc[a.src_mom ? 3 * (int64_t)o : (int64_t)o]);
-    c.s1 = c.s2 = 0.0;
-    if (a.src_mom) {  // wave-uniform; otherwise the momentum sources are the zeros just set
+    // instead of the 24 B that any read of a 24-B row does -- or entry 0 of the plane where the source is uniform, which costs none
+    c.s0 = RDY_LD(&a.extsrc[a.src_mom ? 3 * (int64_t)o : (int64_t)(o & a.mask_s)]);
+    // (s1 / s2 of the water-only mode are the zeros `cur{}` starts with: nothing writes them again during such a launch)
+    if (a.src_mom) {  // wave-uniform
       c.s1 = RDY_LD(&a.extsrc[3 * (int64_t)o + 1]);
       c.s2 = RDY_LD(&a.extsrc[3 * (int64_t)o + 2]);
     }

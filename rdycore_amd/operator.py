@@ -149,6 +149,9 @@ def plan_series_boundary_edges(mesh: RDyMesh, boundaries=None):
     return e[:n.value].copy(), b[:n.value].copy()
 
 
+UNIFORM_SOURCE, UNIFORM_MANNINGS, UNIFORM_FLAT_BED = 1, 2, 4   # bits of Operator.uniform_fields()
+
+
 class Operator:
     """Operator (include/private/rdyoperatorimpl.h:103-201), native MI355X backend."""
 
@@ -704,6 +707,14 @@ class Operator:
         out = C.c_int32()
         _lib.check(_lib.load().rdyhip_source_is_water_only(self._h, C.byref(out)))
         return bool(out.value)
+
+    def uniform_fields(self) -> int:
+        """rdyhip_uniform_fields: the UNIFORM_* bits of the fields whose every owned element is known to hold one value -- the
+        next first-order / HR launch reads element 0 of them instead of the plane (include/rdyhip.h, "Uniform fields").  Reading
+        `external_sources` or `mannings_n` hands out a writable pointer and ends that field's mode for good."""
+        out = C.c_int32()
+        _lib.check(_lib.load().rdyhip_uniform_fields(self._h, C.byref(out)))
+        return int(out.value)
 
     @property
     def mannings_n(self) -> torch.Tensor:

@@ -1,7 +1,7 @@
 """The Euler-step kernels' u_out store policy over a sweep of mesh sizes, IN A TIME LOOP (the two state arrays alternate: what a
 step stores is what the next one reads).  Without the non-temporal hint the new state is still in the Infinity Cache (256 MB)
 when the next step gathers it -- if it fits beside what else lives there; with the hint it comes from HBM.  rdyhip_create picks
-by the size of the state array (RDYHIP_UOUT_CACHED_MAX_MB); this sweep is where that number comes from.
+by the size of the state array (28 MB to 144 MB); this sweep is where that number comes from.
 usage (GPU box): python tools/uout_policy_sweep.py [--hr | --second-order] > gpurun_out/uout_policy_sweep.txt"""
 import os
 import sys
