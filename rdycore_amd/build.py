@@ -14,7 +14,6 @@ CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(CSRC, "librdyhip.so")
 SOURCES = ["rdyhip_api.hip"]
-DEPS = SOURCES + ["error.h", "tile_format.h", "host_layout.h", "operator_state.h", "uniform_fields.h", "field_io.h", "swe_device.h","swe_kernels.h", "forcing_kernels.h", "muscl_kernels.h", "rk_kernels.h", "output_kernels.h", "series_kernels.h", "series_plan.h", "readout_kernels.h", "tracer_kernels.h", "ensemble_kernels.h", "halo_exchange.h", "halo_plan.h"]
 ARCH = "gfx950"
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 
@@ -28,7 +27,8 @@ def needs_build() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, s) for s in DEPS] + [os.path.join(INCLUDE, "rdyhip.h")]
+    # the one translation unit includes every header of csrc/
+    deps = [os.path.join(CSRC, s) for s in os.listdir(CSRC) if s.endswith((".h", ".hip"))] + [os.path.join(INCLUDE, "rdyhip.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

@@ -118,11 +118,7 @@ __global__ __launch_bounds__(BLOCK) void ensemble_rhs_kernel(const KernelArgs a,
           const RiemannSide other = riemann_side(um[3 * n + 0], um[3 * n + 1], um[3 * n + 2], a.tiny_h, a.h_anuga_sq);
           const bool        self_left = coef[s] < 0.0;
           RiemannSide       L, R;
-          L.h = self_left ? self.h : other.h;        R.h = self_left ? other.h : self.h;
-          L.u = self_left ? self.u : other.u;        R.u = self_left ? other.u : self.u;
-          L.v = self_left ? self.v : other.v;        R.v = self_left ? other.v : self.v;
-          L.sqh = self_left ? self.sqh : other.sqh;  R.sqh = self_left ? other.sqh : self.sqh;
-          L.c = self_left ? self.c : other.c;        R.c = self_left ? other.c : self.c;
+          orient_sides(self, other, self_left, L, R);
           fl  = roe_flux(L, R, sn[s], cn[s]);
           wet = !(R.h < a.tiny_h && L.h < a.tiny_h);
         } else {

@@ -46,6 +46,22 @@ static int boundary_edges(RDyHipOperator op, int32_t boundary, int32_t num_edges
   if (*n != num_edges) return fail(RDYHIP_ERR_USER, "num_edges (%d) does not match boundary.num_edges (%d)", num_edges, *n);  // operator.c:1052
   return 0;
 }
+// Whole rows of those edges, `ncomp` doubles each, between the host array and the device table [.][ncomp] that starts at `table`
+// (the SWE, tracer or one ensemble member's boundary values or fluxes): host -> device with `to_device`, else back.  Waits for
+// the device first: the evaluations run on the callers' streams (PETSc's and torch's are non-blocking), and one still in flight
+// may be reading the values a setter replaces or writing the fluxes a getter reads.
+static int boundary_rows_copy(RDyHipOperator op, int32_t boundary, int32_t num_edges, double *table, size_t ncomp, double *host, bool to_device) {
+  int32_t off = 0, n = 0;
+  int     rc  = boundary_edges(op, boundary, num_edges, &off, &n);
+  if (rc || n == 0) return rc;
+  if (!host) return fail(RDYHIP_ERR_USER, to_device ? "null values" : "null output");
+  HIP_TRY(hipDeviceSynchronize());
+  double      *rows  = table + ncomp * (size_t)off;
+  const size_t bytes = sizeof(double) * ncomp * (size_t)n;
+  if (to_device) HIP_TRY(hipMemcpy(rows, host, bytes, hipMemcpyHostToDevice));
+  else HIP_TRY(hipMemcpy(host, rows, bytes, hipMemcpyDeviceToHost));
+  return 0;
+}
 // ... and the components [comp_offset, comp_offset + num_comp) of `values` for them; *n = 0 where there is nothing to write
 static int boundary_values_args(RDyHipOperator op, int32_t boundary, int32_t comp_offset, int32_t num_comp, int32_t num_edges, const double *values,
                                 int32_t *off, int32_t *n) {
@@ -58,18 +74,13 @@ static int boundary_values_args(RDyHipOperator op, int32_t boundary, int32_t com
 }
 
 int rdyhip_set_boundary_values(RDyHipOperator op, int32_t boundary, int32_t comp_offset, int32_t num_comp, int32_t num_edges, const double *values) {
+  if (op && comp_offset == 0 && num_comp == 3) return boundary_rows_copy(op, boundary, num_edges, op->d_bvalues.p, 3, const_cast<double *>(values), true);
   int32_t off = 0, n = 0;
   int     rc  = boundary_values_args(op, boundary, comp_offset, num_comp, num_edges, values, &off, &n);
   if (rc || n == 0) return rc;
-  // the apply calls run on the caller's streams (PETSc's and torch's are non-blocking): an RHS still in flight may be
-  // reading the values this call replaces
-  HIP_TRY(hipDeviceSynchronize());
-  double *dst = op->d_bvalues.p + 3 * (size_t)off;
-  if (comp_offset == 0 && num_comp == 3) {
-    HIP_TRY(hipMemcpy(dst, values, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice));
-  } else {
-    HIP_TRY(hipMemcpy2D(dst + comp_offset, 3 * sizeof(double), values, num_comp * sizeof(double), num_comp * sizeof(double), n, hipMemcpyHostToDevice));
-  }
+  HIP_TRY(hipDeviceSynchronize());   // as boundary_rows_copy
+  HIP_TRY(hipMemcpy2D(op->d_bvalues.p + 3 * (size_t)off + comp_offset, 3 * sizeof(double), values, num_comp * sizeof(double), num_comp * sizeof(double), n,
+                      hipMemcpyHostToDevice));
   return 0;
 }
 

@@ -1,5 +1,5 @@
-// What an operator is made of: the device buffers that free themselves, the staging ring of the stream-ordered setters and
-// RDyHipOperator_s.  Includes the HIP runtime and host_layout.h (for LayoutCounts); included by rdyhip_api.hip only.
+// What an operator is made of: the device buffers that free themselves, the staging ring of the stream-ordered setters, one
+// struct of state per feature and RDyHipOperator_s.  Includes the HIP runtime and host_layout.h (for LayoutCounts); included by rdyhip_api.hip only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -130,6 +130,63 @@ struct Readout {
     if (done) (void)hipEventDestroy(done);
     if (sums_done) (void)hipEventDestroy(sums_done);
   }
+  size_t bytes() const { return d_planes.bytes() + d_area.bytes() + d_records.bytes(); }
+};
+
+// The features below are allocated by their enable call (RK4: the first step) and kept until destroy.  Each is built in a
+// local and moved into the operator once every allocation and copy has succeeded: a failed call leaves nothing behind.
+// bytes(): the device memory held, which rdyhip_layout_info reports.
+
+// rdyhip_rk4_step: the stage state [n_cells][3] and k1..k4 [n_owned][3]; allocated: y.p is set
+struct Rk4Workspace {
+  DevBuf<double> y, k[4];
+  size_t bytes() const { return y.bytes() + k[0].bytes() + k[1].bytes() + k[2].bytes() + k[3].bytes(); }
+};
+
+// rdyhip_output_mean_*: one [n_owned][3] accumulator per enabled variable (bit i of RDYHIP_OUTPUT_*) and the time it spans
+struct OutputMeans {
+  DevBuf<double> acc[3];
+  double         time[3] = {0.0, 0.0, 0.0};
+  size_t bytes() const { return acc[0].bytes() + acc[1].bytes() + acc[2].bytes(); }
+};
+
+// rdyhip_series_*: one device log of WriteTimeSeries, `capacity` records of entries x 3 doubles each, and the time of every
+// record on the host
+struct Series {
+  bool                 enabled = false;
+  int32_t              entries = 0, capacity = 0;
+  DevBuf<double>       d_log;
+  std::vector<double>  times;            // size() = the number of records
+  DevBuf<int32_t>      d_sites;          // observations: [entries] local cell of every site
+  DevBuf<int32_t>      d_slot;           // boundary fluxes: [K] row of boundary edge k in a record, or -1
+  DevBuf<double>       d_len;            //                  [K] edge lengths
+  double               btime = 0.0;      //                  boundary_fluxes.accumulated_time
+  std::vector<int32_t> h_edge, h_bnd;    //                  [entries] local edge id and boundary of every recorded edge
+  size_t bytes() const { return d_log.bytes() + d_sites.bytes() + d_slot.bytes() + d_len.bytes(); }
+};
+
+// rdyhip_tracers_* (tracer_kernels.h): N = 3 + n values per row.  Boundary values and fluxes [K][N] and the tracer sources
+// [n_owned][n] are allocated by rdyhip_tracers_enable, the primitive variables [n_owned][N] by the first
+// rdyhip_tracers_primitive_variables, from which on every tracer evaluation stores them.
+struct TracerState {
+  int32_t        n = 0, riemann = 0;   // 0 tracers: not enabled
+  DevBuf<double> bvalues, bflux, src, pv;
+  bool           pv_wanted = false;
+  size_t bytes() const { return bvalues.bytes() + bflux.bytes() + src.bytes() + pv.bytes(); }
+};
+
+// rdyhip_ensemble_* (ensemble_kernels.h): B members on this operator's mesh, all allocated by rdyhip_ensemble_enable.  The
+// launch is (grid, groups) workgroups, every group walking per_group members (the last one maybe fewer).
+struct EnsembleState {
+  int32_t                    members = 0, groups = 0, per_group = 0;   // 0 members: not enabled
+  DevBuf<double>             mannings, extsrc, bvalues, bflux;   // [B][owned], [B][owned][3], [B][K][3] x 2
+  DevBuf<double>             blk_max;     // [B][ENSEMBLE_WAVES * grid] one Courant bucket per member and wave
+  DevBuf<int32_t>            blk_pos;
+  DevBuf<DeviceCourant>      d_courant;   // [B]
+  std::vector<RDyHipCourant> courant;     // [B] what rdyhip_ensemble_update_diagnostics read last
+  size_t bytes() const {
+    return mannings.bytes() + extsrc.bytes() + bvalues.bytes() + bflux.bytes() + blk_max.bytes() + blk_pos.bytes() + d_courant.bytes();
+  }
 };
 
 struct RDyHipHalo_s;
@@ -205,44 +262,48 @@ struct RDyHipOperator_s : LayoutCounts {
   DevBuf<double>  d_scratch_f;   // F of rdyhip_euler_step when the caller wants none and the kernel cannot skip it
   DevBuf<double>  d_stage_vals;
   DevBuf<int32_t> d_stage_ids;
-  // rdyhip_rk4_step: the stage state [n_cells][3] and k1..k4 [n_owned][3], allocated by the first call, kept until destroy
-  DevBuf<double>  d_rk_y, d_rk_k[4];
-  bool            rk_ready = false;
-  // rdyhip_output_mean_*: one [n_owned][3] accumulator per enabled variable (bit i of RDYHIP_OUTPUT_*) and the time it spans
-  DevBuf<double>  d_out_acc[3];
-  double          out_time[3] = {0.0, 0.0, 0.0};
-  // rdyhip_series_*: the two device logs of WriteTimeSeries (index 0: observations, 1: boundary fluxes), `capacity` records
-  // of entries x 3 doubles each, and the time of every record on the host
-  struct Series {
-    bool                enabled = false;
-    int32_t             entries = 0, capacity = 0;
-    DevBuf<double>      d_log;
-    std::vector<double> times;   // size() = the number of records
-  } series[2];
-  DevBuf<int32_t>      d_ser_sites, d_ser_slot;   // [S] local cell of every site; [K] row of boundary edge k in a record, or -1
-  DevBuf<double>       d_ser_len;                 // [K] edge lengths
-  double               ser_btime = 0.0;           // boundary_fluxes.accumulated_time
-  std::vector<int32_t> h_ser_edge, h_ser_bnd;     // [E] local edge id and boundary of every recorded edge
-  // what the record plan needs of the boundary edges (series_plan.h), kept at create beside h_bedge / h_boff
+  // what the record plan of the boundary-flux series (series_plan.h) and the tracers' enable need of the boundary edges,
+  // kept at create beside h_bedge / h_boff
   std::vector<double>  h_blen;     // [K] edges.lengths
   std::vector<int32_t> h_bghost;   // the boundary edges whose left cell is a ghost
-  // rdyhip_state_read_* / rdyhip_error_sums (declared after `stage`: its copy stream outlives these buffers)
-  Readout readout;
-  // rdyhip_tracers_* (tracer_kernels.h): N = 3 + n_tracers values per row.  Boundary values and fluxes [K][N] and the tracer
-  // sources [n_owned][n_tracers] are allocated by rdyhip_tracers_enable, the primitive variables [n_owned][N] by the first
-  // rdyhip_tracers_primitive_variables, from which on every tracer evaluation stores them.
-  int32_t              n_tracers = 0, tracer_riemann = 0;   // 0 tracers: not enabled
-  DevBuf<double>       d_tr_bvalues, d_tr_bflux, d_tr_src, d_tr_pv;
-  bool                 tr_pv_wanted = false;
   std::vector<int32_t> h_btype;    // [K] condition type of every boundary edge (the tracer path refuses critical outflow)
-  // rdyhip_ensemble_* (ensemble_kernels.h): B members on this operator's mesh, all allocated by rdyhip_ensemble_enable.  The
-  // launch is (grid, ens_groups) workgroups, every group walking ens_per_group members (the last one maybe fewer).
-  int32_t                    ens_members = 0, ens_groups = 0, ens_per_group = 0;   // 0 members: not enabled
-  DevBuf<double>             d_ens_mannings, d_ens_extsrc, d_ens_bvalues, d_ens_bflux;   // [B][owned], [B][owned][3], [B][K][3] x 2
-  DevBuf<double>             d_ens_blk_max;   // [B][ENSEMBLE_WAVES * grid] one Courant bucket per member and wave
-  DevBuf<int32_t>            d_ens_blk_pos;
-  DevBuf<DeviceCourant>      d_ens_courant;   // [B]
-  std::vector<RDyHipCourant> ens_courant;     // [B] what rdyhip_ensemble_update_diagnostics read last
+  // The features (each a struct above, with the device bytes it holds).  `readout` is declared after `stage`: its copy stream
+  // outlives these buffers.
+  Rk4Workspace  rk4;
+  OutputMeans   means;
+  Series        series[2];   // 0: observations, 1: boundary fluxes
+  Readout       readout;
+  TracerState   tracers;
+  EnsembleState ensemble;
 
-  int64_t device_bytes = 0;
+  int64_t device_bytes = 0;   // what rdyhip_create allocated; rdyhip_layout_info adds the features'
+  int64_t feature_bytes() const {
+    return (int64_t)(rk4.bytes() + means.bytes() + series[0].bytes() + series[1].bytes() + readout.bytes() + tracers.bytes() + ensemble.bytes());
+  }
 };
+
+// What every launcher (gradients, RHS, tracers, ensembles) passes of the operator as it is; each sets only its own work,
+// fields and flags on top.  A new field of KernelArgs that all of them need goes here.
+static KernelArgs kernel_args_base(const RDyHipOperator_s *op) {
+  KernelArgs a{};
+  a.n_owned    = op->n_owned;
+  a.stride     = op->stride;
+  a.o2l        = op->prefix ? nullptr : op->d_o2l.p;
+  a.cold       = op->d_cold.p;
+  a.coef       = op->d_coef.p;
+  a.dzdx       = op->d_dzdx.p;
+  a.dzdy       = op->d_dzdy.p;
+  a.tiny_h     = op->config.tiny_h;
+  a.h_anuga_sq = op->config.h_anuga_regular * op->config.h_anuga_regular;
+  a.xq_thresh  = op->config.xq2018_threshold;
+  return a;
+}
+// ... and of a launch that evaluates F(u) for all owned cells, one thread each, in one go (tracers, ensembles)
+static KernelArgs kernel_args_all_cells(const RDyHipOperator_s *op) {
+  KernelArgs a = kernel_args_base(op);
+  a.n_work     = op->n_owned;
+  a.xcd_chunks = op->xcd_chunks;
+  a.overwrite  = 1;
+  a.phase      = RDYHIP_PHASE_ALL;
+  return a;
+}

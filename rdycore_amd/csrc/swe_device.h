@@ -124,10 +124,19 @@ __device__ __forceinline__ RiemannSide riemann_side(double h, double hu, double 
   return s;
 }
 
+// What a flux built on top of the Roe flux needs of its intermediates (the tracer flux, tracer_kernels.h): the two square
+// roots and the reciprocal of their sum, hr - hl, the normal discharges of the two sides, the outer wave terms a1 dw0 and
+// a3 dw2, and the middle eigenvalue.
+struct RoeWaves {
+  double duml, dumr, inv_sum, dh, ql, qr, w0, w2, a2;
+};
+
 // ComputeSWERoeEigenspectrum + ComputeSWERoeFlux for one edge,
 // src/swe/swe_roe_flux_petsc.h:15-81, 103-128.  Same formulas; the divisions
 // by (duml+dumr) and by chat are each done once as a reciprocal.
-__device__ __forceinline__ RoeFlux roe_flux(const RiemannSide &L, const RiemannSide &R, double sn, double cn) {
+// tail(RoeWaves, RoeFlux &) runs once the three components stand: the hook of a flux with further components.
+template <class Tail>
+__device__ __forceinline__ RoeFlux roe_flux_with(const RiemannSide &L, const RiemannSide &R, double sn, double cn, Tail tail) {
   const double hl = L.h, ul = L.u, vl = L.v, hr = R.h, ur = R.u, vr = R.v;
   const double duml = L.sqh, dumr = R.sqh, cl = L.c, cr = R.c;
   const double hhat    = duml * dumr;
@@ -182,7 +191,22 @@ __device__ __forceinline__ RoeFlux roe_flux(const RiemannSide &L, const RiemannS
   out.f0 = 0.5 * (fl0 + fr0 - w0 - 0.0 * w1 - w2);
   out.f1 = 0.5 * (fl1 + fr1 - r10 * w0 - r11 * w1 - r12 * w2);
   out.f2 = 0.5 * (fl2 + fr2 - r20 * w0 - r21 * w1 - r22 * w2);
+  tail(RoeWaves{duml, dumr, inv_sum, dh, ql, qr, w0, w2, a2}, out);
   return out;
+}
+
+__device__ __forceinline__ RoeFlux roe_flux(const RiemannSide &L, const RiemannSide &R, double sn, double cn) {
+  return roe_flux_with(L, R, sn, cn, [](const RoeWaves &, RoeFlux &) {});
+}
+
+// The sides of an interior edge seen from one of its cells: the cell is the left one where its coefficient is negative
+// (the layout comment of rdyhip_api.hip)
+__device__ __forceinline__ void orient_sides(const RiemannSide &self, const RiemannSide &other, bool self_left, RiemannSide &L, RiemannSide &R) {
+  L.h = self_left ? self.h : other.h;        R.h = self_left ? other.h : self.h;
+  L.u = self_left ? self.u : other.u;        R.u = self_left ? other.u : self.u;
+  L.v = self_left ? self.v : other.v;        R.v = self_left ? other.v : self.v;
+  L.sqh = self_left ? self.sqh : other.sqh;  R.sqh = self_left ? other.sqh : self.sqh;
+  L.c = self_left ? self.c : other.c;        R.c = self_left ? other.c : self.c;
 }
 
 struct BoundaryFlux {

@@ -1155,11 +1155,7 @@ __global__ __launch_bounds__(BLOCK) void swe_rhs_kernel(const KernelArgs a, cons
         const RiemannSide other = riemann_side(u[3 * (int64_t)n + 0], u[3 * (int64_t)n + 1], u[3 * (int64_t)n + 2], a.tiny_h, a.h_anuga_sq);
         const bool        self_left = coef < 0.0;
         RiemannSide       L, R;
-        L.h = self_left ? self.h : other.h;        R.h = self_left ? other.h : self.h;
-        L.u = self_left ? self.u : other.u;        R.u = self_left ? other.u : self.u;
-        L.v = self_left ? self.v : other.v;        R.v = self_left ? other.v : self.v;
-        L.sqh = self_left ? self.sqh : other.sqh;  R.sqh = self_left ? other.sqh : self.sqh;
-        L.c = self_left ? self.c : other.c;        R.c = self_left ? other.c : self.c;
+        orient_sides(self, other, self_left, L, R);
         fl  = roe_flux(L, R, sn, cn);
         wet = !(R.h < a.tiny_h && L.h < a.tiny_h);
       } else {

@@ -8,9 +8,10 @@
 // registers (a run-time tracer count would put them in scratch).  A row's 3 + NT doubles are loaded and stored back to back.
 //
 // The flow part reuses the operator's own tables through KernelArgs / ColdArgs (slot tables, Manning n, the [owned][3]
-// external source, the Courant buckets); what only this path has travels in TracerArgs.  Nothing in swe_device.h,
-// swe_kernels.h or muscl_kernels.h is changed: their inline functions are called, roe_flux() is restated here because the
-// tracer flux needs the eigenvalues and wave strengths it does not hand out.
+// external source, the Courant buckets); what only this path has travels in TracerArgs.  The inline functions of
+// swe_device.h and swe_kernels.h are called as they are; the flow part of the flux is roe_flux_with() (swe_device.h), whose
+// hook hands the tracer components the eigenvalue and wave terms they need (roe_flux() itself is the same body with an
+// empty hook, so the SWE kernels' machine code is what it was).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -48,7 +49,7 @@ __device__ __forceinline__ void tracer_concentrations(double h, const double *hc
 }
 
 // ComputeTracerRoeFlux / ComputeUpwindTracerRoeFlux (tracer_roe_flux_petsc.h:17-119, 129-206) for one edge.  The flow
-// components are ComputeSWERoeFlux in the arithmetic of roe_flux() (swe_device.h), operation for operation; tracer j adds
+// components are ComputeSWERoeFlux as roe_flux_with() (swe_device.h) evaluates it; in its hook tracer j adds
 //   Roe:     cihat = (sqrt(hl) cl + sqrt(hr) cr) / (sqrt(hl) + sqrt(hr)),  dW_j = (cr hr - cl hl) - cihat (hr - hl),
 //            flux_j = 0.5 (hl uperp_l cl + hr uperp_r cr) - 0.5 (cihat A0 dW0 + cihat A2 dW2 + A1 dW_j)
 //   upwind:  flux_j = F_h (F_h >= 0 ? cl : cr), F_h the Roe mass flux
@@ -56,65 +57,20 @@ __device__ __forceinline__ void tracer_concentrations(double h, const double *hc
 template <int NT, bool UPWIND>
 __device__ __forceinline__ double tracer_roe_flux(const RiemannSide &L, const RiemannSide &R, const double *cl_, const double *cr_, double sn, double cn,
                                                   double *fl) {
-  const double hl = L.h, ul = L.u, vl = L.v, hr = R.h, ur = R.u, vr = R.v;
-  const double duml = L.sqh, dumr = R.sqh, cl = L.c, cr = R.c;
-  const double hhat    = duml * dumr;
-  const double inv_sum = rdy_rcp(duml + dumr);
-  const double uhat    = sum_of_products(duml, ul, dumr, ur) * inv_sum;
-  const double vhat    = sum_of_products(duml, vl, dumr, vr) * inv_sum;
-  const SqrtPair cp       = rdy_sqrt_rsqrt(0.5 * GRAVITY * (hl + hr));
-  const double   chat     = cp.s;
-  const double   inv_chat = cp.r;
-  const double uperp   = sum_of_products(uhat, cn, vhat, sn);
-
-  const double dh     = hr - hl;
-  const double du     = ur - ul;
-  const double dv     = vr - vl;
-  const double dupar  = -du * sn + dv * cn;
-  const double duperp = du * cn + dv * sn;
-
-  const double r10 = uhat - chat * cn, r11 = -sn, r12 = uhat + chat * cn;
-  const double r20 = vhat - chat * sn, r21 = cn, r22 = vhat + chat * sn;
-
-  const double uperpl = ul * cn + vl * sn;
-  const double uperpr = ur * cn + vr * sn;
-  double       a1     = fabs(uperp - chat);
-  const double a2     = fabs(uperp);
-  double       a3     = fabs(uperp + chat);
-
-  // critical flow fix
-  const double da1 = fmax(0.0, 2.0 * ((uperpr - cr) - (uperpl - cl)));
-  if (a1 < da1) a1 = 0.5 * (a1 * a1 / da1 + da1);
-  const double da3 = fmax(0.0, 2.0 * ((uperpr + cr) - (uperpl + cl)));
-  if (a3 < da3) a3 = 0.5 * (a3 * a3 / da3 + da3);
-
-  const double t   = hhat * duperp * inv_chat;
-  const double dw0 = 0.5 * (dh - t);
-  const double dw1 = hhat * dupar;
-  const double dw2 = 0.5 * (dh + t);
-
-  const double gh2l = 0.5 * GRAVITY * hl * hl, gh2r = 0.5 * GRAVITY * hr * hr;
-  const double ql = uperpl * hl, qr = uperpr * hr;
-  const double fl1 = ul * ql + gh2l * cn;
-  const double fl2 = vl * ql + gh2l * sn;
-  const double fr1 = ur * qr + gh2r * cn;
-  const double fr2 = vr * qr + gh2r * sn;
-
-  const double w0 = a1 * dw0, w1 = a2 * dw1, w2 = a3 * dw2;
-  fl[0] = 0.5 * (ql + qr - w0 - 0.0 * w1 - w2);
-  fl[1] = 0.5 * (fl1 + fr1 - r10 * w0 - r11 * w1 - r12 * w2);
-  fl[2] = 0.5 * (fl2 + fr2 - r20 * w0 - r21 * w1 - r22 * w2);
+  const RoeFlux f = roe_flux_with(L, R, sn, cn, [&](const RoeWaves &w, const RoeFlux &o) {
 #pragma unroll
-  for (int j = 0; j < NT; ++j) {
-    if (UPWIND) {
-      fl[3 + j] = fl[0] * (fl[0] >= 0.0 ? cl_[j] : cr_[j]);
-    } else {
-      const double cihat = sum_of_products(duml, cl_[j], dumr, cr_[j]) * inv_sum;
-      const double dwj   = (cr_[j] * hr - cl_[j] * hl) - cihat * dh;
-      fl[3 + j]          = 0.5 * (ql * cl_[j] + qr * cr_[j] - cihat * w0 - cihat * w2 - a2 * dwj);
+    for (int j = 0; j < NT; ++j) {
+      if (UPWIND) {
+        fl[3 + j] = o.f0 * (o.f0 >= 0.0 ? cl_[j] : cr_[j]);
+      } else {
+        const double cihat = sum_of_products(w.duml, cl_[j], w.dumr, cr_[j]) * w.inv_sum;
+        const double dwj   = (cr_[j] * R.h - cl_[j] * L.h) - cihat * w.dh;
+        fl[3 + j]          = 0.5 * (w.ql * cl_[j] + w.qr * cr_[j] - cihat * w.w0 - cihat * w.w2 - w.a2 * dwj);
+      }
     }
-  }
-  return chat + fabs(uperp);
+  });
+  fl[0] = f.f0, fl[1] = f.f1, fl[2] = f.f2;
+  return f.amax;
 }
 
 // One thread = one owned cell: the cell's own row is prepared once, its up to S slots are walked in slot order, the source
@@ -170,11 +126,7 @@ __global__ __launch_bounds__(BLOCK) void tracer_rhs_kernel(const KernelArgs a, c
         tracer_concentrations<NT>(oth[0], oth + 3, a.tiny_h, other_c);
         const bool  self_left = coef < 0.0;
         RiemannSide L, R;
-        L.h = self_left ? self.h : other.h;        R.h = self_left ? other.h : self.h;
-        L.u = self_left ? self.u : other.u;        R.u = self_left ? other.u : self.u;
-        L.v = self_left ? self.v : other.v;        R.v = self_left ? other.v : self.v;
-        L.sqh = self_left ? self.sqh : other.sqh;  R.sqh = self_left ? other.sqh : self.sqh;
-        L.c = self_left ? self.c : other.c;        R.c = self_left ? other.c : self.c;
+        orient_sides(self, other, self_left, L, R);
         double cl[NT], cr[NT];
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
