@@ -800,7 +800,8 @@ int rdyhip_error_sums_get(RDyHipOperator op, RDyHipErrorSums *out);
  * Stated differences: the flux of a boundary edge is stored for edges whose left cell is owned; rows of edges behind ghost cells
  *   are left as they are.  There is no accumulated-flux array (the reference's tracer boundary operator keeps none).  On a rank
  *   with ghost cells the Courant diagnostic covers the edges of the owned cells with len / area_self only: edges between two
- *   ghosts, and the len / area of a ghost that is the smaller cell of a cut edge, do not enter.
+ *   ghosts, and the len / area of a ghost that is the smaller cell of a cut edge, do not enter; the cell reported for a cut edge
+ *   is the owned one.  The maximum over the ranks is still the whole mesh's: the smaller cell of every cut edge is owned by someone.
  * Ghost rows of 3 + NT values travel through rdyhip_pack_rows / rdyhip_unpack_rows; the halo object's fused steps, the output
  * means, the time series and the read-out cover the three flow components of the SWE state only.
  * Every argument error (a null operator, tracers not enabled, a null array where one is needed, a tracer or boundary index out of
@@ -849,7 +850,8 @@ int rdyhip_tracers_get_boundary_fluxes(RDyHipOperator op, int32_t boundary, int3
  *   ranks with ghost cells.
  * Stated differences: there is no accumulated boundary-flux array.  Primitive variables and the flux divergence are not stored.
  *   The flux of a boundary edge is stored where its left cell is owned; rows of edges behind ghost cells are left as they are.  On
- *   a rank with ghost cells the Courant diagnostic covers the edges of the owned cells with len / area_self only.  The SWE entry
+ *   a rank with ghost cells the Courant diagnostic covers the edges of the owned cells with len / area_self only, and the cell
+ *   reported for a cut edge is the owned one.  The SWE entry
  *   points of an operator with the ensemble enabled behave exactly as before and share no array with it.
  * Every argument error -- a null operator, num_members outside 1..RDYHIP_MAX_ENSEMBLE_MEMBERS, an operator created with
  *   second_order or hydrostatic reconstruction, a second enable, any other call before enable, a member, boundary or component

@@ -161,7 +161,7 @@ extern "C" int rdyhip_ensemble_update_diagnostics(RDyHipOperator op, void *strea
   DeviceCourant dc[RDYHIP_MAX_ENSEMBLE_MEMBERS];
   HIP_TRY(hipMemcpyAsync(dc, op->ensemble.d_courant.p, sizeof(DeviceCourant) * (size_t)B, hipMemcpyDeviceToHost, (hipStream_t)stream));
   HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-  for (int m = 0; m < B; ++m) op->ensemble.courant[m] = courant_from_device(op, dc[m]);
+  for (int m = 0; m < B; ++m) op->ensemble.courant[m] = courant_from_device(op, dc[m], true);
   return 0;
 }
 

@@ -257,7 +257,9 @@ struct RDyHipOperator_s : LayoutCounts {
   std::vector<int32_t> h_internal_edge, h_edge_cells, h_bedge, h_boff;
   std::vector<int64_t> h_cell_gid, h_edge_gid;
   std::vector<double>  h_area;
+  std::vector<uint8_t> h_owned;   // [num_cells] cells.is_owned, kept on a rank with ghost cells only
   RDyHipCourant        courant{0.0, -1, -1};
+  bool                 courant_owned_side = false;   // the buckets hold a tracer evaluation's numbers (courant_from_device)
   // staging buffers for the setters
   DevBuf<double>  d_scratch_f;   // F of rdyhip_euler_step when the caller wants none and the kernel cannot skip it
   DevBuf<double>  d_stage_vals;

@@ -160,6 +160,7 @@ int launch_rhs(RDyHipOperator op, int32_t phase, int32_t overwrite, int reset_di
                bool gradients_ready = false, double *u_out = nullptr, int bucket_half = 0, const hipStream_t *joined_on = nullptr) {
   // joined_on: the caller's stream, where `st` is the library's exchange stream (the halo launch of a two-stream step)
   if (!op) return fail(RDYHIP_ERR_USER, "null operator");
+  if (reset_diag) op->courant_owned_side = false;
   // an Euler-step launch rewrites the attached halo's send buffer (tiles flagged TILE_SEND_FLAG): whatever it held is gone
   // (rdyhip_euler_step_overlapped notes the new content itself once its launches are enqueued)
   if (u_out && op->fused_halo) halo_forget_packed_state(op->fused_halo);
@@ -470,6 +471,10 @@ int rdyhip_create(const RDyHipConfig *config, const RDyHipMesh *mesh, int32_t nu
   op->h_boff    = std::move(L.boff);
   op->h_tile_c0 = std::move(L.tile_c0);
   if (!L.prefix) op->h_l2o.assign(mesh->cell_local_to_owned, mesh->cell_local_to_owned + nc);
+  if (nc > no) {
+    op->h_owned.resize(nc);
+    for (size_t c = 0; c < nc; ++c) op->h_owned[c] = mesh->cell_is_owned[c] ? 1 : 0;
+  }
   if (mesh->cell_global_ids) op->h_cell_gid.assign(mesh->cell_global_ids, mesh->cell_global_ids + nc);
   if (mesh->edge_global_ids) op->h_edge_gid.assign(mesh->edge_global_ids, mesh->edge_global_ids + L.ne);
 
@@ -636,11 +641,14 @@ int rdyhip_reset_diagnostics(RDyHipOperator op, void *stream) {
   hipLaunchKernelGGL(courant_reset_kernel, dim3(4), dim3(1024), 0, (hipStream_t)stream, (int)op->d_blk_max.n, op->d_blk_max.p, op->d_blk_pos.p);
   HIP_TRY(hipGetLastError());
   op->courant = RDyHipCourant{0.0, -1, -1};
+  op->courant_owned_side = false;
   return 0;
 }
 
-// the device's (value, position in the reference's loop order) as the value and the global ids of its edge and cell
-static RDyHipCourant courant_from_device(RDyHipOperator op, const DeviceCourant &dc) {
+// the device's (value, position in the reference's loop order) as the value and the global ids of its edge and cell.
+// owned_side: the number comes from a kernel that looks at a cut edge from its owned cell only, with len / area_self (tracers,
+// ensembles: include/rdyhip.h); the cell of such an edge is then the owned one, whatever the area of the ghost behind it
+static RDyHipCourant courant_from_device(RDyHipOperator op, const DeviceCourant &dc, bool owned_side = false) {
   RDyHipCourant out{dc.max_courant, -1, -1};
   if (dc.pos >= 0) {
     int32_t edge, cell;
@@ -648,6 +656,10 @@ static RDyHipCourant courant_from_device(RDyHipOperator op, const DeviceCourant 
       edge             = op->h_internal_edge[dc.pos];
       const int32_t l  = op->h_edge_cells[2 * (size_t)edge], r = op->h_edge_cells[2 * (size_t)edge + 1];
       cell             = (op->h_area[l] < op->h_area[r]) ? l : r;  // swe_petsc.c:294-295
+      if (owned_side && !op->h_owned.empty()) {
+        if (!op->h_owned[l]) cell = r;
+        else if (!op->h_owned[r]) cell = l;
+      }
     } else {
       const int32_t k = dc.pos - op->n_internal;
       edge            = op->h_bedge[k];
@@ -668,7 +680,7 @@ int rdyhip_update_diagnostics(RDyHipOperator op, void *stream) {
   DeviceCourant dc;
   HIP_TRY(hipMemcpyAsync(&dc, op->d_courant.p, sizeof(dc), hipMemcpyDeviceToHost, (hipStream_t)stream));
   HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-  op->courant = courant_from_device(op, dc);
+  op->courant = courant_from_device(op, dc, op->courant_owned_side);
   return 0;
 }
 

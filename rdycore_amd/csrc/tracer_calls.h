@@ -36,6 +36,7 @@ int tracers_check(RDyHipOperator op) {
 int launch_tracers(RDyHipOperator op, double dt, const double *u, double *f, double *u_out, hipStream_t st) {
   if (op->n_owned == 0) return 0;   // a rank may own nothing: nothing to launch
   op->courant = RDyHipCourant{0.0, -1, -1};
+  op->courant_owned_side = true;   // rdyhip_update_diagnostics: the cell of a cut edge is the owned one
   KernelArgs a = kernel_args_all_cells(op);
   a.mannings   = op->d_mannings.p;
   a.extsrc     = op->d_extsrc.p;   // the canonical [owned][3] array, whatever the water-only mode of the SWE kernels says

@@ -108,3 +108,43 @@ def interior_courant_numbers(case):
         amax = np.sqrt(0.5 * g * (hl + hr)) + np.abs(uhat * m.edge_cn[e] + vhat * m.edge_sn[e])
         c = amax * m.edge_lengths[e] / np.minimum(m.cell_areas[l], m.cell_areas[r]) * case.dt
     return np.where(skip, np.nan, c)
+
+
+def loop_edges(mesh):
+    """(edge, cell) per position of the reference's Courant loop: the internal edges in edges.internal_edge_ids order with the
+    cell of the smaller area (the right one where the areas are equal, src/swe/swe_petsc.c:294-295), then the boundaries' edge
+    lists one after another with their left cell.  Local ids."""
+    m = mesh
+    e = np.asarray(m.edge_internal_ids, dtype=np.int64)
+    l, r = m.edge_cell_ids[2 * e], m.edge_cell_ids[2 * e + 1]
+    be = np.concatenate([np.asarray(b.edge_ids, dtype=np.int64) for b in m.boundaries] + [np.zeros(0, dtype=np.int64)])
+    return np.concatenate([e, be]), np.concatenate([np.where(m.cell_areas[l] < m.cell_areas[r], l, r), m.edge_cell_ids[2 * be]])
+
+
+def owned_side_courant_numbers(mesh, c_interior, c_boundary):
+    """The Courant numbers the tracer and ensemble kernels form on a rank with ghost cells, as include/rdyhip.h documents them:
+    every owned cell looks at every edge of its own and forms amax len / area_self dt; an edge dry on both sides is skipped, an
+    edge between two ghosts never enters, and neither does the len / area of a ghost that is the smaller cell of a cut edge.
+    `c_interior`: the reference's number per internal edge (loop order, amax len / min(area_l, area_r) dt, NaN where skipped:
+    interior_courant_numbers, TracerReference.edge_courant); `c_boundary`: per boundary edge (amax len / area_left dt:
+    test_gpu_ensemble.boundary_courant_numbers).  The side with the smaller area keeps the reference's number as it is, the other
+    side's is scaled by min(area) / area_self, so on a mesh without ghosts the maximum over an edge's sides IS the reference's.
+    Returns one row per (edge, owned cell): (c, loop position, local edge, local cell), skipped edges left out."""
+    m = mesh
+    owned = m.cell_is_owned != 0
+    area = m.cell_areas
+    e = np.asarray(m.edge_internal_ids, dtype=np.int64)
+    l, r = m.edge_cell_ids[2 * e], m.edge_cell_ids[2 * e + 1]
+    amin = np.minimum(area[l], area[r])
+    c_interior, c_boundary = np.asarray(c_interior, dtype=np.float64), np.asarray(c_boundary, dtype=np.float64)
+    be = np.concatenate([np.asarray(b.edge_ids, dtype=np.int64) for b in m.boundaries] + [np.zeros(0, dtype=np.int64)])
+    bl = m.edge_cell_ids[2 * be]
+    assert c_interior.shape == e.shape and c_boundary.shape == be.shape
+    rows = []
+    for cell in (l, r):
+        c = np.where(area[cell] == amin, c_interior, c_interior * (amin / area[cell]))
+        rows.append((np.where(owned[cell], c, np.nan), np.arange(e.size), e, cell))
+    rows.append((np.where(owned[bl], c_boundary, np.nan), e.size + np.arange(be.size), be, bl))
+    c, pos, edge, cell = (np.concatenate([row[k] for row in rows]) for k in range(4))
+    keep = np.isfinite(c)
+    return c[keep], pos[keep], edge[keep], cell[keep]

@@ -16,11 +16,13 @@ from rdycore_amd import mesh as M
 from rdycore_amd.operator import RDyFlowConfig
 
 
-def tracer_case(rng, mesh, nt, riemann, tiny=True, h_anuga=0.0, region_block=0):
+def tracer_case(rng, mesh, nt, riemann, tiny=True, h_anuga=0.0, region_block=0, tiny_h=None):
     """a random_case of the SWE fuzz tests (wet / dry / thin films, friction, slopes, sources, Dirichlet data; region_block > 0:
     the classes of cell in runs, which makes wet/dry fronts) with its critical-outflow boundaries made reflecting, widened by
-    `nt` tracers; returns (case, reference, state [num_cells, 3 + nt]).  Also used by test_gpu_tracers.py."""
-    case = RC.random_case(rng, mesh, RDyFlowConfig(h_anuga_regular=h_anuga), region_block=region_block)
+    `nt` tracers; returns (case, reference, state [num_cells, 3 + nt]).  tiny_h: the wet/dry threshold, None: the default of
+    RDyFlowConfig.  Also used by the GPU tests of the tracer kernel."""
+    cfg = RDyFlowConfig(h_anuga_regular=h_anuga) if tiny_h is None else RDyFlowConfig(h_anuga_regular=h_anuga, tiny_h=tiny_h)
+    case = RC.random_case(rng, mesh, cfg, region_block=region_block)
     case.condition_types = [M.CONDITION_REFLECTING if t == M.CONDITION_CRITICAL_OUTFLOW else t for t in case.condition_types]
     if not tiny:
         case.u_local[case.cell_kind == RC.KIND_TINY] = 0.0
