@@ -395,6 +395,39 @@ int rdyhip_reset_diagnostics(RDyHipOperator op, void *stream);
 int rdyhip_update_diagnostics(RDyHipOperator op, void *stream);
 int rdyhip_get_diagnostics(RDyHipOperator op, RDyHipCourant *courant);
 
+/* ---- diagnostics, non-blocking ----------------------------------------------
+ * The read-back of the Courant record(s) in two halves, so that a host with an adaptive time step can prepare the next
+ * coupling interval (RDyApplyForcing takes the time only, src/rdyadvance.c:351) beside the device and collect the 16 bytes
+ * where it needs dt.  `scope` names whose record is read: RDYHIP_DIAGNOSTICS_OPERATOR is what rdyhip_update_diagnostics
+ * reports (the most recent SWE or tracer evaluations), RDYHIP_DIAGNOSTICS_ENSEMBLE what rdyhip_ensemble_update_diagnostics
+ * reports (B structs).  The two scopes are independent.
+ * rdyhip_diagnostics_begin: enqueues on `stream` the merge launch of the blocking call, a copy of the record(s) into pinned
+ *   memory the operator owns, and an event; returns without waiting for anything.  The pinned memory and the event are
+ *   allocated by the first begin of a scope: only that call may synchronise.
+ * rdyhip_diagnostics_wait: blocks on that event only, resolves the edge and cell ids as the blocking call does and stores the
+ *   result where rdyhip_get_diagnostics / rdyhip_ensemble_get_diagnostics read it.
+ * rdyhip_diagnostics_ready: *ready = 1 once the copy has landed (an event query; also after the wait), else 0.  It never
+ *   stands in for the wait: only the wait delivers the result.
+ * Place in the stream: the result is that of begin's place in `stream`.  Evaluations enqueued afterwards, their diagnostics
+ *   reset and rdyhip_reset_diagnostics do not change what the wait delivers, and what resolving the ids needs (whether the
+ *   numbers are a tracer evaluation's, which a later SWE evaluation would change) is remembered as of begin.  An evaluation
+ *   or reset called after the wait resets what the getters return, as always.
+ * One read per scope: a begin while an earlier one of the same scope has not been waited for replaces it -- not an error.  The
+ *   new launch is first ordered behind the earlier copy (hipStreamWaitEvent), also when the two are on different streams: the
+ *   device record is never rewritten under a running copy.
+ * Nothing to wait for: a wait with no read in flight -- no begin yet, or a read that was already waited for or discarded -- is
+ *   RDYHIP_ERR_USER; so is ready before any begin or after a discard.  Neither call touches an event that was not recorded.
+ * The blocking calls keep their behaviour bit for bit.  A read of their scope that is in flight is discarded by them: a later
+ *   wait is RDYHIP_ERR_USER, and the blocking call's result stands.
+ * rdyhip_destroy waits for a copy still in flight before it frees the pinned memory.
+ * A null operator, an unknown scope, or the ensemble scope before rdyhip_ensemble_enable is RDYHIP_ERR_USER before any device
+ *   call.  A rank that owns nothing behaves as the blocking calls do there: (0, -1, -1). */
+#define RDYHIP_DIAGNOSTICS_OPERATOR 0   /* what rdyhip_update_diagnostics reports: SWE or tracer evaluations */
+#define RDYHIP_DIAGNOSTICS_ENSEMBLE 1   /* what rdyhip_ensemble_update_diagnostics reports: B structs */
+int rdyhip_diagnostics_begin(RDyHipOperator op, int32_t scope, void *stream);
+int rdyhip_diagnostics_ready(RDyHipOperator op, int32_t scope, int32_t *ready);
+int rdyhip_diagnostics_wait(RDyHipOperator op, int32_t scope);
+
 /* ---- halo helpers (DMGlobalToLocalBegin/End, src/rdysetup.c:1133-1134) -------
  * pack:   buf[i][0..2] = u_local[cell_ids[i]][0..2]   (cells a neighbour rank needs)
  * unpack: u_local[cell_ids[i]][0..2] = buf[i][0..2]   (this rank's ghost cells)

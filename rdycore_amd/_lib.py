@@ -98,6 +98,9 @@ SYMBOLS = {
     "rdyhip_reset_diagnostics": (C.c_int, [_H, C.c_void_p]),
     "rdyhip_update_diagnostics": (C.c_int, [_H, C.c_void_p]),
     "rdyhip_get_diagnostics": (C.c_int, [_H, C.POINTER(RDyHipCourant)]),
+    "rdyhip_diagnostics_begin": (C.c_int, [_H, C.c_int32, C.c_void_p]),
+    "rdyhip_diagnostics_ready": (C.c_int, [_H, C.c_int32, c_int32_p]),
+    "rdyhip_diagnostics_wait": (C.c_int, [_H, C.c_int32]),
     "rdyhip_pack_cells": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "rdyhip_unpack_cells": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "rdyhip_pack_rows": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),

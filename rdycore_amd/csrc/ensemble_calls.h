@@ -154,6 +154,8 @@ extern "C" int rdyhip_ensemble_get_boundary_fluxes(RDyHipOperator op, int32_t me
 extern "C" int rdyhip_ensemble_update_diagnostics(RDyHipOperator op, void *stream) {
   int rc = ensemble_check(op);
   if (rc) return rc;
+  rc = diagnostics_read_discard(op->diag_read[RDYHIP_DIAGNOSTICS_ENSEMBLE], (hipStream_t)stream);
+  if (rc) return rc;
   const int B = op->ensemble.members;
   hipLaunchKernelGGL(ensemble_courant_finalize_kernel, dim3(B), dim3(BLOCK), 0, (hipStream_t)stream, ENSEMBLE_WAVES * op->grid, op->ensemble.blk_max.p,
                      op->ensemble.blk_pos.p, op->ensemble.d_courant.p);

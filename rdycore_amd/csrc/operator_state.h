@@ -133,6 +133,25 @@ struct Readout {
   size_t bytes() const { return d_planes.bytes() + d_area.bytes() + d_records.bytes(); }
 };
 
+// One non-blocking read of the Courant record(s) (rdyhip_diagnostics_begin / _ready / _wait; diagnostics_calls.h), one per
+// scope: the pinned record(s) the copy lands in, the event recorded behind the copy, and what resolving the ids needs as of
+// begin.  Pinned memory and event are allocated by the first begin of the scope; `done` is touched only while IN_FLIGHT.
+struct DiagnosticsRead {
+  enum State { NONE, IN_FLIGHT, LANDED };   // NONE: never begun, or discarded by the blocking call; LANDED: waited for
+  DeviceCourant *h_rec = nullptr;   // pinned: 1 record (operator scope) or RDYHIP_MAX_ENSEMBLE_MEMBERS (ensemble scope)
+  hipEvent_t     done = nullptr;
+  State          state = NONE;
+  bool           owned_side = false;  // courant_owned_side at begin
+  DiagnosticsRead() = default;
+  DiagnosticsRead(const DiagnosticsRead &) = delete;
+  DiagnosticsRead &operator=(const DiagnosticsRead &) = delete;
+  ~DiagnosticsRead() {
+    if (state == IN_FLIGHT) (void)hipEventSynchronize(done);   // the copy writes h_rec
+    if (h_rec) (void)hipHostFree(h_rec);
+    if (done) (void)hipEventDestroy(done);
+  }
+};
+
 // The features below are allocated by their enable call (RK4: the first step) and kept until destroy.  Each is built in a
 // local and moved into the operator once every allocation and copy has succeeded: a failed call leaves nothing behind.
 // bytes(): the device memory held, which rdyhip_layout_info reports.
@@ -277,6 +296,7 @@ struct RDyHipOperator_s : LayoutCounts {
   Readout       readout;
   TracerState   tracers;
   EnsembleState ensemble;
+  DiagnosticsRead diag_read[2];   // RDYHIP_DIAGNOSTICS_OPERATOR, RDYHIP_DIAGNOSTICS_ENSEMBLE
 
   int64_t device_bytes = 0;   // what rdyhip_create allocated; rdyhip_layout_info adds the features'
   int64_t feature_bytes() const {

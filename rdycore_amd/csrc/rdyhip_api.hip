@@ -671,8 +671,17 @@ static RDyHipCourant courant_from_device(RDyHipOperator op, const DeviceCourant 
   return out;
 }
 
+// A non-blocking read (diagnostics_calls.h) that nobody waited for is given up: work enqueued on `st` from here on runs behind
+// its copy, which may still be reading the device record from another stream
+static int diagnostics_read_discard(DiagnosticsRead &r, hipStream_t st) {
+  if (r.state == DiagnosticsRead::IN_FLIGHT) HIP_TRY(hipStreamWaitEvent(st, r.done, 0));
+  r.state = DiagnosticsRead::NONE;
+  return 0;
+}
+
 int rdyhip_update_diagnostics(RDyHipOperator op, void *stream) {
   if (!op) return fail(RDYHIP_ERR_USER, "null operator");
+  if (int rc = diagnostics_read_discard(op->diag_read[RDYHIP_DIAGNOSTICS_OPERATOR], (hipStream_t)stream)) return rc;
   // the RHS launches keep one running (max, first position) bucket per workgroup slot; they are merged only here
   hipLaunchKernelGGL(courant_finalize_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, (int)op->d_blk_max.n, op->d_blk_max.p, op->d_blk_pos.p,
                      op->d_courant.p);
@@ -788,4 +797,5 @@ int rdyhip_layout_info(RDyHipOperator op, RDyHipLayoutInfo *info) {
 #include "readout_calls.h"
 #include "tracer_calls.h"
 #include "ensemble_calls.h"
+#include "diagnostics_calls.h"
 

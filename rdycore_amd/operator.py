@@ -33,6 +33,7 @@ SERIES_OBSERVATIONS, SERIES_BOUNDARY_FLUXES = 1, 2                      # RDYHIP
 COMPONENT_H, COMPONENT_HU, COMPONENT_HV = 1, 2, 4                       # RDYHIP_COMPONENT_*: the planes of the state read-out
 MAX_TRACERS = 7                                                         # RDYHIP_MAX_TRACERS
 TRACER_RIEMANN_ROE, TRACER_RIEMANN_UPWIND_ROE = 0, 1                    # RDYHIP_TRACER_RIEMANN_*
+DIAGNOSTICS_OPERATOR, DIAGNOSTICS_ENSEMBLE = 0, 1                       # RDYHIP_DIAGNOSTICS_*: the scopes of the non-blocking read-back
 
 
 @dataclasses.dataclass
@@ -573,6 +574,13 @@ class Operator:
     def ensemble_update_diagnostics(self):
         _lib.check(_lib.load().rdyhip_ensemble_update_diagnostics(self._h, _stream()))
 
+    def ensemble_diagnostics_begin(self):
+        """the non-blocking half of ensemble_update_diagnostics (rdyhip_diagnostics_begin, ensemble scope), on the current stream"""
+        _lib.check(_lib.load().rdyhip_diagnostics_begin(self._h, DIAGNOSTICS_ENSEMBLE, _stream()))
+
+    def ensemble_diagnostics_wait(self):
+        _lib.check(_lib.load().rdyhip_diagnostics_wait(self._h, DIAGNOSTICS_ENSEMBLE))
+
     def ensemble_get_diagnostics(self) -> list:
         """rdyhip_ensemble_get_diagnostics: one CourantNumberDiagnostics per member"""
         c = (_lib.RDyHipCourant * max(self.num_members, 1))()
@@ -738,6 +746,21 @@ class Operator:
         c = _lib.RDyHipCourant()
         _lib.check(_lib.load().rdyhip_get_diagnostics(self._h, C.byref(c)))
         return CourantNumberDiagnostics(c.max_courant_num, c.global_edge_id, c.global_cell_id)
+
+    # the same read-back in two halves (rdyhip_diagnostics_*): begin enqueues the merge launch, a 16-byte copy into pinned
+    # memory and an event on the current stream and returns; wait blocks on that event alone and stores what get_diagnostics
+    # returns.  The result is that of begin's place in the stream.
+    def diagnostics_begin(self):
+        _lib.check(_lib.load().rdyhip_diagnostics_begin(self._h, DIAGNOSTICS_OPERATOR, _stream()))
+
+    def diagnostics_ready(self) -> bool:
+        """an event query; it never stands in for diagnostics_wait"""
+        r = C.c_int32(0)
+        _lib.check(_lib.load().rdyhip_diagnostics_ready(self._h, DIAGNOSTICS_OPERATOR, C.byref(r)))
+        return bool(r.value)
+
+    def diagnostics_wait(self):
+        _lib.check(_lib.load().rdyhip_diagnostics_wait(self._h, DIAGNOSTICS_OPERATOR))
 
     # -- explicit Euler update kept on the device ----------------------------
     def axpy_owned(self, dt: float, f_global: torch.Tensor, u_local: torch.Tensor):

@@ -24,7 +24,8 @@ evaluations, with the state kept on the GPU.
   * RDyAdvance (src/rdyadvance.c:261-383): advance to the next coupling time
     with the last step shortened to land on it (TS_EXACTFINALTIME_MATCHSTEP),
     and, when adaptive time stepping is on, rescale dt from the previous
-    interval's maximum Courant number (303-343).
+    interval's maximum Courant number (303-343).  `pipelined=True` takes the read-back of that number in two halves
+    (rdyhip_diagnostics_begin / _wait): the forcing of the next interval is applied before the host waits for it.
 """
 from __future__ import annotations
 
@@ -87,8 +88,15 @@ class EulerStepper:
     """the explicit TS of RDyAdvance: forward Euler (default) or, with temporal="rk4", classical Runge-Kutta"""
 
     def __init__(self, op, halo=None, adaptive: Optional[AdaptiveTime] = None, fused: bool = True, forcing=None, temporal: str = "euler",
-                 means: int = 0, series: Optional[TimeSeries] = None):
-        """`series`: a TimeSeries, or None (the default): none of the operator's series calls is made.  With one, the stepper
+                 means: int = 0, series: Optional[TimeSeries] = None, pipelined: bool = False):
+        """`pipelined` (with `adaptive`; default False: the call sequence of RDyAdvance, unchanged): advance() ends with the
+        operator's diagnostics_begin() instead of the blocking update_diagnostics(), and the NEXT advance() applies the forcing
+        first -- RDyApplyForcing takes the time only -- and only then collects: diagnostics_wait(), reduce_courant() across
+        ranks, the dt rule; then reset_diagnostics() and the steps.  The host so prepares interval k + 1 while the device
+        finishes interval k.  The dt sequence, and with it the trajectory, is the same bits.  `max_courant` and `courant`
+        collect on first access (on several ranks that is a collective: read them on all ranks or on none), and finish()
+        collects at the end of a run.  Without `adaptive` no diagnostics call is made at all.
+        `series`: a TimeSeries, or None (the default): none of the operator's series calls is made.  With one, the stepper
         plays WriteTimeSeries (src/time_series.c:530-564): one monitor call before the first step of its life (step 0) and one
         after every step, each doing, in this order,
           1. observations: if observation_interval is nonzero and step % observation_interval == 0, a record of the current
@@ -122,8 +130,10 @@ class EulerStepper:
         self.adaptive = adaptive
         self.time = 0.0
         self.step = 0
-        self.max_courant = None      # diagnostics of the last interval, all ranks (None = not updated yet)
-        self.courant = None          # the whole struct (value + global edge / cell id of the maximum)
+        self.pipelined = bool(pipelined)
+        self._pending = None         # pipelined: the device of a diagnostics_begin() that has not been collected yet
+        self._max_courant = None     # diagnostics of the last interval, all ranks (None = not updated yet)
+        self._courant = None         # the whole struct (value + global edge / cell id of the maximum)
         self._f = None
         self.means = int(means)
         if self.means:
@@ -135,6 +145,29 @@ class EulerStepper:
                 op.enable_observation_series(series.observation_sites, series.capacity)
             if series.boundary_flux_interval:
                 op.enable_boundary_flux_series(series.capacity, series.boundaries)
+
+    def _collect(self):
+        """pipelined: the second half of UpdateOperatorDiagnostics for the read the last advance() began, if any"""
+        if self._pending is None:
+            return
+        device, self._pending = self._pending, None
+        self.op.diagnostics_wait()
+        self._courant = reduce_courant(self.op.get_diagnostics(), device)
+        self._max_courant = self._courant.max_courant_num
+
+    def finish(self):
+        """collects the diagnostics of the last interval of a run (pipelined; otherwise there is nothing left to collect)"""
+        self._collect()
+
+    @property
+    def max_courant(self):
+        self._collect()
+        return self._max_courant
+
+    @property
+    def courant(self):
+        self._collect()
+        return self._courant
 
     def _series_monitor(self, dt, state):
         """WriteTimeSeries(ts, step, time, X) for the step count and time the stepper stands at"""
@@ -174,17 +207,21 @@ class EulerStepper:
         if self._f is None or self._f.shape[0] != self.op.mesh.num_owned_cells:
             self._f = torch.empty((self.op.mesh.num_owned_cells, 3), dtype=torch.float64, device=u_local.device)
         a = self.adaptive
-        if a is not None and self.max_courant is not None:
+        if self.pipelined and self.forcing is not None:
+            self.forcing.apply(self.time)       # nothing in it depends on dt: staged while the device finishes the last interval
+        self._collect()
+        cmax = self._max_courant
+        if a is not None and cmax is not None:
             # src/rdyadvance.c:308-330: rescaled whenever the diagnostics are valid; a zero Courant number (nothing
             # wet) makes target / max infinite there, i.e. the factor is max_increase_factor
-            if self.max_courant < a.target_courant_number:
-                ratio = a.target_courant_number / self.max_courant if self.max_courant > 0.0 else float("inf")
+            if cmax < a.target_courant_number:
+                ratio = a.target_courant_number / cmax if cmax > 0.0 else float("inf")
                 dt *= min(ratio, a.max_increase_factor)
                 dt = min(dt, interval)
             else:
-                dt *= a.target_courant_number / self.max_courant
+                dt *= a.target_courant_number / cmax
         t_end = self.time + interval
-        if self.forcing is not None:
+        if self.forcing is not None and not self.pipelined:
             self.forcing.apply(self.time)
         self.op.reset_diagnostics()
         if self.halo is not None and getattr(self.halo, "_halo", None) is not None:
@@ -226,11 +263,14 @@ class EulerStepper:
                 self._series_monitor(dt, cur if self.temporal == "euler" and self.fused else u_local)
         if cur is not u_local:
             u_local.copy_(cur)                   # an odd number of steps ended in the second buffer (euler, fused)
-        if a is not None:
+        if a is not None and self.pipelined:
+            self.op.diagnostics_begin()          # collected by the next advance(), by finish() or on first access
+            self._pending = u_local.device
+        elif a is not None:
             # UpdateOperatorDiagnostics: local 16-byte copy + the MPI_Allreduce(max) of src/operator.c:879
             self.op.update_diagnostics()
-            self.courant = reduce_courant(self.op.get_diagnostics(), u_local.device)
-            self.max_courant = self.courant.max_courant_num
+            self._courant = reduce_courant(self.op.get_diagnostics(), u_local.device)
+            self._max_courant = self._courant.max_courant_num
         return dt
 
     def _rk4_step(self, h: float, u_local: torch.Tensor):
