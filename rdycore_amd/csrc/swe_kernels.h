@@ -150,6 +150,38 @@ __device__ __forceinline__ T load_uniform(const T *p, int i) {
   return ((ConstPtr)(uintptr_t)p)[i];
 }
 
+// Unit-stride accesses of the tiled kernels: element (wave-uniform index) + (lane) of an array, as a 64-bit SCALAR base -- the
+// array plus the uniform part, made with scalar adds next to the access -- and a 32-bit lane offset in bytes that does not change
+// from tile to tile (4 tid, 8 tid, the row offset of the store phase): `global_load v, v_off, s[base:base+1]`.  Written as
+// array[uniform + lane], hipcc builds the 64-bit address per lane and per tile instead (a move of each scalar half into a VGPR,
+// a sign extension, a 64-bit shift-and-add: two to three VALU instructions per access).  The base goes through an empty asm:
+// otherwise the optimiser folds base + lane back into one 64-bit lane index.  As a GLOBAL address: through a generic pointer
+// the access becomes a flat one, which every lgkmcnt wait -- scalar loads, LDS -- then waits for as well.
+//      The "+s" operand needs a base that hipcc can PROVE wave-uniform.  Where it cannot -- every base here is uniform, but an
+// unrelated edit can hide that from the divergence analysis: a single `if (threadIdx.x == 0)` store at kernel entry (the probe,
+// tools/probes/wg_times.patch) does, in the 44 instantiations without the dynamic walk -- the compile fails, loudly, with
+// "illegal VGPR to SGPR copy" reported at the kernel's signature.  The measured fallback is one line ahead of the asm:
+//   b = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)b) | ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(b >> 32)) << 32);
+// (the builtin returns a SIGNED int: without the uint32_t casts the low half is sign-extended over the high one and every base
+// with bit 31 set is a wild address).  It compiles everywhere and leaves the C3 kernel as it is (797 loop VALU), but costs the
+// Euler-step kernels of that family 18 VALU-issued instructions per tile (826 -> 844: 40 more lane operations in the kernel),
+// so it is not in the product (profiles/RESULTS_LOG.md section 27).
+template <typename T>
+using GlobalPtr = __attribute__((address_space(1))) T *;
+template <typename T>
+__device__ __forceinline__ GlobalPtr<T> lane_ptr(T *uniform_base, uint32_t lane_bytes) {
+  uint64_t b = (uint64_t)uniform_base;
+  asm("" : "+s"(b));
+  return (GlobalPtr<T>)(b + lane_bytes);
+}
+// The lane offset tid << log2(bytes), made where it is used from a shift count the optimiser cannot see: as a loop-invariant
+// value it is hoisted out of the tile loop with its zero-extension -- a VGPR pair per offset held for the launch, and a 64-bit
+// vector add per access again, because the extension is no longer in the block of the access.
+__device__ __forceinline__ uint32_t lane_bytes(int tid, int log2_bytes) {
+  asm volatile("" : "+s"(log2_bytes));
+  return (uint32_t)tid << log2_bytes;
+}
+
 // a field of the device-resident ColdArgs block: one scalar load at the point of use
 #define RDY_COLD(a, field) (load_uniform(&(a).cold->field, 0))
 
@@ -284,8 +316,10 @@ __device__ __forceinline__ RowTranspose row_transpose_slots(double *wave_plane0,
   t.rd = wave_plane0 + lane;
   return t;
 }
+// `rows`: the array at the TILE's first row, wave-uniform; `row_bytes`: where the lane's element of the wave's first 64 lies
+// behind it, 8 (3 (tid - lane) + lane) -- a scalar base and a 32-bit lane offset (lane_ptr), the three stores 512 B apart.
 template <int PLANE, bool NT = true>
-__device__ __forceinline__ void wave_store_rows3_lds(double *__restrict__ arr, int64_t base, int lane, int ncell, const RowTranspose &t, double v0, double v1,
+__device__ __forceinline__ void wave_store_rows3_lds(double *rows, uint32_t row_bytes, int lane, int ncell, const RowTranspose &t, double v0, double v1,
                                                      double v2) {
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // the reads of the array before this one come first
   __builtin_amdgcn_wave_barrier();
@@ -295,18 +329,28 @@ __device__ __forceinline__ void wave_store_rows3_lds(double *__restrict__ arr, i
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();
   const double s0 = t.rd[0], s1 = t.rd[PLANE], s2 = t.rd[2 * PLANE];
-  double *row = arr + (base + lane);
   // element 64 k + lane belongs to cell (64 k + lane) / 3 of the wave: stored if that cell exists, i.e. 64 k + lane < 3 ncell
+  // (the address is formed under each predicate: formed once ahead of the three, it is a 64-bit vector add and a VGPR pair)
   const int e = 3 * ncell - lane;
   if (NT) {
-    if (e > 0) RDY_ST(&row[0], s0);
-    if (e > 64) RDY_ST(&row[64], s1);
-    if (e > 128) RDY_ST(&row[128], s2);
+    if (e > 0) RDY_ST(lane_ptr(rows, row_bytes), s0);
+    if (e > 64) RDY_ST(lane_ptr(rows, row_bytes) + 64, s1);
+    if (e > 128) RDY_ST(lane_ptr(rows, row_bytes) + 128, s2);
   } else {
-    if (e > 0) row[0] = s0;
-    if (e > 64) row[64] = s1;
-    if (e > 128) row[128] = s2;
+    if (e > 0) *lane_ptr(rows, row_bytes) = s0;
+    if (e > 64) lane_ptr(rows, row_bytes)[64] = s1;
+    if (e > 128) lane_ptr(rows, row_bytes)[128] = s2;
   }
+}
+
+// What a lane WITHOUT a cell carries into the store phase.  It takes part in the wave's transpose like every other lane, and
+// the rows it writes there are masked at the store (wave_store_rows3_lds: element e is stored only if its cell exists; the
+// scattered u_out rows sit under the lane's own `active`), so the values are read by nobody.  They are whatever the registers
+// hold: an empty asm names them as its outputs, which defines them for the compiler without an instruction -- zeroing them
+// cost the tile loop eighteen 32-bit registers' worth of moves per tile.
+__device__ __forceinline__ void rows_unset(double (&out)[6], double (&acc)[3], double &hu, double &hv) {
+  asm volatile("" : "=v"(out[0]), "=v"(out[1]), "=v"(out[2]), "=v"(out[3]), "=v"(out[4]), "=v"(out[5]), "=v"(acc[0]), "=v"(acc[1]), "=v"(acc[2]),
+               "=v"(hu), "=v"(hv));
 }
 
 // A thread's running Courant maximum over the tiles it walks (swe_petsc.c:289-296: the reference keeps the FIRST edge in
@@ -497,33 +541,58 @@ __device__ __forceinline__ StreamArgs stream_args(HotArgs k) {
 // Only the lanes that hold a cell load, and only they read `c` afterwards: phase 2 runs under the same count (tid < td.nc())
 // and the arrival points name registers, not values.  The other lanes' registers are left as they are -- setting them cost
 // ten moves per tile.
+// The lane's cell is c_off + tid: every address is a scalar base (array + the tile's first cell, lane_ptr) plus the lane's
+// 4 tid or 8 tid; a uniform field's mask (0 / -1) goes on both parts, so that every lane reads element 0.
 template <int S, bool HR>
-__device__ __forceinline__ void load_streams(const StreamArgs &a, int o, bool active, CellStreams<S> &c) {
+__device__ __forceinline__ void load_streams(const StreamArgs &a, int c_off, int tid, bool active, CellStreams<S> &c) {
   if (active) {
+    const uint32_t t4 = lane_bytes(tid, 2), t8 = lane_bytes(tid, 3);
+    const int64_t  o0 = c_off;
     if (S == 3) {
-      c.r0 = RDY_LD(&reinterpret_cast<const uint32_t *>(a.slot_ref)[o]);
+      c.r0 = RDY_LD(lane_ptr(reinterpret_cast<const uint32_t *>(a.slot_ref) + o0, t4));
     } else {
-      const uint2 w = reinterpret_cast<const uint2 *>(a.slot_ref)[o];
+      typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+      const u32x2 w = *lane_ptr(reinterpret_cast<const u32x2 *>(a.slot_ref) + o0, t8);
       c.r0          = w.x;
       c.r1          = w.y;
     }
 #pragma unroll
-    for (int s = 0; s < S; ++s) c.coef[s] = RDY_LD(&a.coef[s * a.stride + o]);
+    for (int s = 0; s < S; ++s) c.coef[s] = RDY_LD(lane_ptr(a.coef + (s * a.stride + o0), t8));
     if (!HR) {  // under HR the pressure correction of the flux carries the bed slope
-      c.dzdx = RDY_LD(&a.dzdx[o & a.mask_dz]);
-      c.dzdy = RDY_LD(&a.dzdy[o & a.mask_dz]);
+      const int64_t  oz = c_off & a.mask_dz;
+      const uint32_t tz = t8 & (uint32_t)a.mask_dz;
+      c.dzdx = RDY_LD(lane_ptr(a.dzdx + oz, tz));
+      c.dzdy = RDY_LD(lane_ptr(a.dzdy + oz, tz));
     } else {
       c.dzdx = c.dzdy = 0.0;
     }
-    c.nman = RDY_LD(&a.mannings[o & a.mask_n]);
+    c.nman = RDY_LD(lane_ptr(a.mannings + (int64_t)(c_off & a.mask_n), t8 & (uint32_t)a.mask_n));
     // the water source: row o of the [owned][3] array, or entry o of the water plane, which costs 8 B of HBM traffic per cell
     // instead of the 24 B that any read of a 24-B row does -- or entry 0 of the plane where the source is uniform, which costs none
-    c.s0 = RDY_LD(&a.extsrc[a.src_mom ? 3 * (int64_t)o : (int64_t)(o & a.mask_s)]);
+    // (one load for both forms, its base and the lane's stride chosen with scalar code)
+    const int32_t  ms  = a.src_mom ? -1 : a.mask_s;
+    const double  *src = a.extsrc + (a.src_mom ? 3 * o0 : (int64_t)(c_off & ms));
+    const uint32_t ts  = ((a.src_mom ? 24u : 8u) * (uint32_t)tid) & (uint32_t)ms;
+    c.s0 = RDY_LD(lane_ptr(src, ts));
     // (s1 / s2 of the water-only mode are the zeros `cur{}` starts with: nothing writes them again during such a launch)
     if (a.src_mom) {  // wave-uniform
-      c.s1 = RDY_LD(&a.extsrc[3 * (int64_t)o + 1]);
-      c.s2 = RDY_LD(&a.extsrc[3 * (int64_t)o + 2]);
+      c.s1 = RDY_LD(lane_ptr(src, ts) + 1);
+      c.s2 = RDY_LD(lane_ptr(src, ts) + 2);
     }
+  }
+}
+
+// The two rounds of a tile's edge records, each under the count phase 1 tests; a lane without a record keeps what it has.
+// The second round is the same lane offset against a base TILE records further on.
+__device__ __forceinline__ void load_records(const KernelArgs &a, int e_off, int ne, int tid, uint32_t &lr0, double &cs0, uint32_t &lr1, double &cs1) {
+  const int64_t e0 = e_off;
+  if (tid < ne) {
+    lr0 = RDY_LD(lane_ptr(a.e_lr + e0, lane_bytes(tid, 2)));
+    cs0 = RDY_LD(lane_ptr(a.e_cs + e0, lane_bytes(tid, 3)));
+  }
+  if (tid + TILE < ne) {
+    lr1 = RDY_LD(lane_ptr(a.e_lr + (e0 + TILE), lane_bytes(tid, 2)));
+    cs1 = RDY_LD(lane_ptr(a.e_cs + (e0 + TILE), lane_bytes(tid, 3)));
   }
 }
 
@@ -740,26 +809,21 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(tiled_bloc
         if (HR) pz = a.zc_local[c];
       }
       if (tid < td.nh()) {
-        const int hc = a.hcells[td.h_off + tid];
+        const int hc = *lane_ptr(a.hcells + (int64_t)td.h_off, lane_bytes(tid, 2));
         ph0 = u[3 * (int64_t)hc + 0]; ph1 = u[3 * (int64_t)hc + 1]; ph2 = u[3 * (int64_t)hc + 2];
         if (HR) phz = a.zc_local[hc];
       }
       const int ne = td.ne();
-      if (tid < ne) { lr0 = RDY_LD(&a.e_lr[td.e_off + tid]); cs0 = RDY_LD(&a.e_cs[td.e_off + tid]); }
-      if (tid + TILE < ne) { lr1 = RDY_LD(&a.e_lr[td.e_off + TILE + tid]); cs1 = RDY_LD(&a.e_cs[td.e_off + TILE + tid]); }
-      load_streams<S, HR>(stream_args(hot_kernargs()), o, tid < td.nc(), cur);
+      load_records(a, td.e_off, ne, tid, lr0, cs0, lr1, cs1);
+      load_streams<S, HR>(stream_args(hot_kernargs()), td.c_off, tid, tid < td.nc(), cur);
     }
-    // the loop positions of the tile's records 0 and COURANT_Q (sorted by position): what lets the Courant tie path dismiss a
-    // candidate without touching memory (CourantTrack); fetched a tile ahead like everything else
-    int      pos_lo = load_uniform(RDY_COLD(a, e_pos), td.e_off);
-    int      pos_q  = load_uniform(RDY_COLD(a, e_pos), td.e_off + min(COURANT_Q, td.ne() - 1));
     int      idx1 = next_valid(idx + step, skips());
     int      tile1 = 0, hid1 = 0, c1 = 0;  // next tile: this thread's halo cell and own cell (local ids)
     TileDesc td1 = td;
     if (idx1 < hi) {
       tile1 = tile_at(idx1);
       td1   = tile_desc(tile1);
-      if (tid < td1.nh()) hid1 = a.hcells[td1.h_off + tid];
+      if (tid < td1.nh()) hid1 = *lane_ptr(a.hcells + (int64_t)td1.h_off, lane_bytes(tid, 2));
       const int o1 = td1.c_off + tid;
       c1           = (a.o2l && tid < td1.nc()) ? a.o2l[o1] : o1;
     }
@@ -827,17 +891,14 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(tiled_bloc
           if (DYN && walk_t == TILE_WALK_DYNAMIC && tid == 0) drawn = draw(ctr_t, (blockIdx.x & 7) * TILE_DRAW_STRIDE);
           tile2 = tile_at(idx2);
           td2   = tile_desc(tile2);
-          if (tid < td2.nh()) hid2 = a.hcells[td2.h_off + tid];
+          if (tid < td2.nh()) hid2 = *lane_ptr(a.hcells + (int64_t)td2.h_off, lane_bytes(tid, 2));
           const int o2 = td2.c_off + tid;
           c2           = (a.o2l && tid < td2.nc()) ? a.o2l[o2] : o2;
         }
       }
       // (b) the next tile's cell states, edge records and per-cell streams
-      int      npos_lo = 0, npos_q = 0;
       if (idx1 < hi) {
         const double *const ub = hot_kernargs()->u;  // fetched beside the tile descriptor, not held across the loop
-        npos_lo = load_uniform(RDY_COLD(a, e_pos), td1.e_off);
-        npos_q  = load_uniform(RDY_COLD(a, e_pos), td1.e_off + min(COURANT_Q, td1.ne() - 1));
         if (tid < td1.nc()) {
           pu0 = ub[3 * (int64_t)c1 + 0]; pu1 = ub[3 * (int64_t)c1 + 1]; pu2 = ub[3 * (int64_t)c1 + 2];
           if (HR) pz = a.zc_local[c1];
@@ -847,8 +908,7 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(tiled_bloc
           if (HR) phz = a.zc_local[hid1];
         }
         const int ne1 = td1.ne();
-        if (tid < ne1) { nlr0 = RDY_LD(&a.e_lr[td1.e_off + tid]); ncs0 = RDY_LD(&a.e_cs[td1.e_off + tid]); }
-        if (tid + TILE < ne1) { nlr1 = RDY_LD(&a.e_lr[td1.e_off + TILE + tid]); ncs1 = RDY_LD(&a.e_cs[td1.e_off + TILE + tid]); }
+        load_records(a, td1.e_off, ne1, tid, nlr0, ncs0, nlr1, ncs1);
       }
       __builtin_amdgcn_s_setprio(0);
 
@@ -943,9 +1003,10 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(tiled_bloc
       double *const    f_hot = hk->f, *const pv_hot = hk->a.pv, *const fdiv_hot = hk->a.fdiv, *const uout_hot = hk->a.u_out;
 
       // ---- phase 2: per-cell sum in the reference's edge order, source terms; the stores come last
-      double out[6]      = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // F[3], then the primitive variables (h, u, v)
-      double acc_fdiv[3] = {0.0, 0.0, 0.0};
-      double own_hu = 0.0, own_hv = 0.0;  // EULER only
+      double out[6];       // F[3], then the primitive variables (h, u, v)
+      double acc_fdiv[3];
+      double own_hu, own_hv;  // EULER only
+      rows_unset(out, acc_fdiv, own_hu, own_hv);
       if (active) {
         double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0;
         if (!OVW) {  // ApplyOperator semantics: add into f (and let the friction term see it)
@@ -991,7 +1052,16 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(tiled_bloc
         }
         if (trk.rec != rec_in) trk.pos = -1;
         // cold: which of the equal edges comes first in the reference's loop (CourantTrack).  Dismissed at once where the
-        // incumbent's position is known and smaller than every position of this tile.
+        // incumbent's position is known and smaller than every position of this tile.  The tile's two bounds -- the loop
+        // positions of its records 0 and COURANT_Q (sorted by position) -- are read HERE, with scalar loads, by the waves
+        // that have a tie: fetched a tile ahead and rotated with the pipeline they were two scalars live across the whole
+        // loop, which cost every tile more than this path costs the few that take it.
+        int pos_lo = 0, pos_q = 0;
+        if (tie) {
+          const int32_t *e_pos = RDY_COLD(a, e_pos);
+          pos_lo               = load_uniform(e_pos, td.e_off);
+          pos_q                = load_uniform(e_pos, td.e_off + min(COURANT_Q, ne - 1));
+        }
         if (tie && !(trk.pos >= 0 && trk.pos < pos_lo)) {
           int first = -1;  // the first slot of this cell at the running maximum: the only one that can come before the incumbent
 #pragma unroll
@@ -1035,38 +1105,37 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(tiled_bloc
                    "v"(hid2), "v"(c2));
       // rotate the pipeline registers, store
       const bool send_tile = EULER && td.send();  // wave-uniform
-      const int  tile_cur  = tile, nc_cur = td.nc();
+      const int  tile_cur  = tile, nc_cur = td.nc(), c_off_cur = td.c_off;
       idx = idx1; tile = tile1; td = td1;
       idx1 = idx2; tile1 = tile2; td1 = td2; hid1 = hid2; c1 = c2;
-      pos_lo = npos_lo;
-      pos_q  = npos_q;
       lr0 = nlr0; lr1 = nlr1; cs0 = ncs0; cs1 = ncs1;
       // the next tile's per-cell streams, into the registers phase 2 (its cold Courant tie path included) has just read
       // for the last time; not on the workgroup's last tile
-      load_streams<S, HR>(sa, td.c_off + tid, !last && tid < td.nc(), cur);
+      load_streams<S, HR>(sa, td.c_off, tid, !last && tid < td.nc(), cur);
       __builtin_amdgcn_sched_barrier(0);
       // F, pv (and fdiv, u_out) are [cell][3]: a wave's 64 cells own 192 consecutive doubles of each.  The rows are
       // transposed through wave shuffles so that every store instruction writes 512 contiguous bytes (whole lines)
       // instead of 64 x 8 bytes at a 24-byte stride -- with the non-temporal hint the strided partial lines reach HBM
       // unmerged (0.58 GB written for 0.48 GB of output).  All 64 lanes take part, cells past the end are masked.
       {
-        const int     lane  = tid & 63;
-        const int64_t base  = 3 * ((int64_t)o - lane);
-        const int     ncell = nc_cur - (tid - lane);  // the wave's cells of this tile
+        const int      lane  = tid & 63;
+        const int64_t  row0  = 3 * (int64_t)c_off_cur;  // the tile's first row: array + row0 is a scalar base
+        const uint32_t rowb  = lane_bytes(3 * tid - 2 * lane, 3);
+        const int      ncell = nc_cur - (tid - lane);  // the wave's cells of this tile
         // the transpose goes through the wave's own 64 entries of sd_v, sd_sq and sd_c (wave_store_rows3_lds): phase 1 read
         // them for the last time before the second barrier, out[5] has this lane's sd_v, phase 0 of the next tile rewrites them
         const RowTranspose rt = row_transpose_slots<nside>(sd_v + (tid - lane), lane);
-        if (!EULER || f_hot) wave_store_rows3_lds<nside, FNT>(f_hot, base, lane, ncell, rt, out[0], out[1], out[2]);
+        if (!EULER || f_hot) wave_store_rows3_lds<nside, FNT>(f_hot + row0, rowb, lane, ncell, rt, out[0], out[1], out[2]);
         // the primitive variables only once somebody has asked for them (KernelArgs::pv); a branch with ONE arm, like fdiv's
-        if (pv_hot) wave_store_rows3_lds<nside>(pv_hot, base, lane, ncell, rt, out[3], out[4], out[5]);
-        if (fdiv_hot) wave_store_rows3_lds<nside>(fdiv_hot, base, lane, ncell, rt, acc_fdiv[0], acc_fdiv[1], acc_fdiv[2]);
+        if (pv_hot) wave_store_rows3_lds<nside>(pv_hot + row0, rowb, lane, ncell, rt, out[3], out[4], out[5]);
+        if (fdiv_hot) wave_store_rows3_lds<nside>(fdiv_hot + row0, rowb, lane, ncell, rt, acc_fdiv[0], acc_fdiv[1], acc_fdiv[2]);
         if (EULER) {
           const double n0 = out[3] + dt * out[0], n1 = own_hu + dt * out[1], n2 = own_hv + dt * out[2];
           if (!a.o2l) {
             // u_out is what the NEXT step reads.  With the hint it is not in the Infinity Cache then; without it, it is -- if it
             // fits: a 2.8 M-cell part (67 MB of state) steps 8 % faster with plain stores, a 10 M-cell one (240 MB of a 256 MB
             // cache) 3.5 % slower (profiles/r04_uout_store_policy.txt).  FNT = false is the instantiation for states that fit.
-            wave_store_rows3_lds<nside, FNT>(uout_hot, base, lane, ncell, rt, n0, n1, n2);
+            wave_store_rows3_lds<nside, FNT>(uout_hot + row0, rowb, lane, ncell, rt, n0, n1, n2);
           } else if (active) {  // owned cells are not a prefix of the local numbering: scattered rows
             const int64_t c = a.o2l[o];
             if constexpr (FNT) {

@@ -3,6 +3,10 @@
 Needs a PROBE build of the library (tools/probes/wg_times.patch applied to a copy of rdycore_amd/csrc, built like
 rdycore_amd/build.py builds the real one): thread 0 of every workgroup stores wall_clock64() (100 MHz) at entry and after its
 last tile, rdyhip_probe_wg_times() copies the [grid][2] table out.  The patch never goes into the library proper.
+(Since the tile loop takes its addresses from scalar bases the patch also puts a readfirstlane of both halves of the base into
+lane_ptr, with unsigned casts: with the entry store in place hipcc cannot prove the bases uniform in the kernels without the
+dynamic walk and would refuse to compile them.  The headline kernel of such a build is the product's instruction stream plus
+the two stores.  That form of the patch applies and compiles; it has not been run on a GPU yet, RESULTS_LOG section 27.)
 
     RDYHIP_LIB=/path/to/probe.so python tools/dyn_tiles_probe.py --walks static,dynamic --out wg_times.json [--label L]
 
