@@ -500,14 +500,19 @@ int32_t rdyhip_halo_direct_receive(RDyHipHalo halo);
 int rdyhip_halo_fuse_pack(RDyHipHalo halo, int32_t enable);
 int32_t rdyhip_halo_pack_fused(RDyHipHalo halo);
 /* which form the steps of a halo take and why (see above); kind: RDYHIP_HALO_STEP_RHS = rdyhip_rhs_overlapped,
- * RDYHIP_HALO_STEP_EULER = rdyhip_euler_step_overlapped */
+ * RDYHIP_HALO_STEP_EULER = rdyhip_euler_step_overlapped, RDYHIP_HALO_STEP_TRACERS_RHS = rdyhip_halo_tracers_rhs,
+ * RDYHIP_HALO_STEP_TRACERS_EULER = rdyhip_halo_tracers_euler_step (each kind has a trial and a choice of its own).  The two
+ * tracer kinds stay in order -- rdyhip_halo_set_form leaves them at form 0, rdyhip_halo_form_info says
+ * RDYHIP_HALO_FORM_LOCKED_IN_ORDER -- on a halo whose pattern receives into owned rows and on a halo without peers. */
 #define RDYHIP_HALO_STEP_RHS 0
 #define RDYHIP_HALO_STEP_EULER 1
+#define RDYHIP_HALO_STEP_TRACERS_RHS 2
+#define RDYHIP_HALO_STEP_TRACERS_EULER 3
 #define RDYHIP_HALO_FORM_TRIAL_RUNNING 0   /* the first calls still alternate */
 #define RDYHIP_HALO_FORM_MEASURED 1        /* the faster form of the trial */
 #define RDYHIP_HALO_FORM_FORCED 2          /* environment or rdyhip_halo_set_form */
 #define RDYHIP_HALO_FORM_DEFAULT 3         /* nothing to choose (no peers) or no timing available: in order */
-#define RDYHIP_HALO_FORM_LOCKED_IN_ORDER 4 /* fused pack with a send cell outside the ghost-adjacent tiles */
+#define RDYHIP_HALO_FORM_LOCKED_IN_ORDER 4 /* fused pack with a send cell outside the ghost-adjacent tiles; tracer kinds: see above */
 typedef struct {
   int32_t form;           /* 0: in order on the caller's stream, 1: two streams */
   int32_t source;         /* RDYHIP_HALO_FORM_* */
@@ -819,7 +824,7 @@ int rdyhip_error_sums_get(RDyHipOperator op, RDyHipErrorSums *out);
  * arrays which the tracer calls neither read nor write.
  *
  * rdyhip_tracers_rhs_function: F is overwritten and never read, the diagnostics start anew (one launch).  There is no accumulate
- *   form and no phased form (RDYHIP_PHASE_ALL only).
+ *   form; the phased forms are rdyhip_tracer_phase_* below.
  * rdyhip_tracers_euler_step: u_local_out[owned rows] = fma(dt, F, u_local) for all 3 + NT components, not in place; the ghost
  *   rows of u_local_out are left alone; with f_global == NULL F is never stored.
  * rdyhip_tracers_primitive_variables: the [owned][3 + NT] array (h, u, v, c_0 ...): velocities in the ANUGA form
@@ -835,8 +840,33 @@ int rdyhip_error_sums_get(RDyHipOperator op, RDyHipErrorSums *out);
  *   with ghost cells the Courant diagnostic covers the edges of the owned cells with len / area_self only: edges between two
  *   ghosts, and the len / area of a ghost that is the smaller cell of a cut edge, do not enter; the cell reported for a cut edge
  *   is the owned one.  The maximum over the ranks is still the whole mesh's: the smaller cell of every cut edge is owned by someone.
- * Ghost rows of 3 + NT values travel through rdyhip_pack_rows / rdyhip_unpack_rows; the halo object's fused steps, the output
- * means, the time series and the read-out cover the three flow components of the SWE state only.
+ * Ghost rows of 3 + NT values travel through the halo object (rdyhip_halo_tracers_* below, rdyhip_halo_exchange with
+ * ncomp = 3 + NT) or through rdyhip_pack_rows / rdyhip_unpack_rows; the output means, the time series and the read-out cover
+ * the three flow components of the SWE state only.
+ *
+ * On several ranks (a partitioned mesh; DMGlobalToLocalBegin/End of OperatorRHSFunction, src/rdysetup.c:1133-1134, ahead of
+ * the tracer operators of src/tracer/tracer_petsc.c):
+ *   rdyhip_tracer_phase_rhs / rdyhip_tracer_phase_euler_step   rdyhip_tracers_rhs_function / _euler_step restricted to
+ *       RDYHIP_PHASE_INTERIOR (owned cells without a ghost neighbour) or RDYHIP_PHASE_HALO (with one); RDYHIP_PHASE_ALL with
+ *       RDYHIP_PHASE_RESET_DIAGNOSTICS is exactly the unphased call.  `flags`: RDYHIP_PHASE_RESET_DIAGNOSTICS starts the Courant
+ *       diagnostic anew, without it the launch merges into it (larger value, then the earlier edge of the reference's loop), so
+ *       INTERIOR with the flag followed by HALO without it reports what one call over all cells reports;
+ *       RDYHIP_PHASE_OVERWRITE is implied and accepted, any other bit is refused.  Rows of cells of the other phase -- F, the
+ *       primitive variables, u_local_out, boundary fluxes -- are not touched.  A HALO call on a rank without ghost-adjacent cells
+ *       launches nothing; with the reset flag it still restarts the diagnostic.
+ *   rdyhip_halo_tracers_rhs / rdyhip_halo_tracers_euler_step   the ghost update of the [num_cells][3 + NT] state and the
+ *       evaluation in one call, as rdyhip_rhs_overlapped / rdyhip_euler_step_overlapped are for the SWE state.  In order: pack,
+ *       transfer, unpack of 3 + NT values per cell on `stream`, then ONE launch.  Two streams: the exchange on the halo's
+ *       stream, the INTERIOR launch on `stream` meanwhile (enqueued before a transport callback is called, behind an RCCL
+ *       group), the join, the HALO launch on `stream`.  The form is chosen per kind by the halo's trial
+ *       (RDYHIP_HALO_STEP_TRACERS_RHS / _EULER).  Direct receive applies as it is.  The fused pack does not extend to tracer
+ *       rows: a tracer step always packs, and the next rdyhip_euler_step_overlapped packs again.  A halo created after
+ *       rdyhip_tracers_enable has buffers of max(3 or 6, 3 + NT) values per cell; on one created before, the first tracer step
+ *       grows them -- it waits for what the halo's stream and `stream` still run, the only call of the tracer path that may
+ *       synchronise -- and rdyhip_halo_exchange(halo, rows, 3 + NT, ...) works from then on.  A rank that owns nothing
+ *       launches nothing but takes part in the exchange.
+ *   Refused with RDYHIP_ERR_USER before any device call: a null operator or halo, tracers not enabled, a halo of another
+ *   operator, a null u_local on a rank with cells, u_local_out == u_local (or null), an unknown phase, unknown flag bits.
  * Every argument error (a null operator, tracers not enabled, a null array where one is needed, a tracer or boundary index out of
  * range, num_edges not the boundary's) is RDYHIP_ERR_USER and is reported before any device call.  A rank that owns nothing
  * launches nothing and succeeds. */
@@ -851,6 +881,14 @@ int rdyhip_tracers_rhs_function(RDyHipOperator op, double dt, const double *u_lo
 int rdyhip_tracers_euler_step(RDyHipOperator op, double dt, const double *u_local, double *u_local_out, double *f_global /* may be NULL */, void *stream);
 int rdyhip_tracers_primitive_variables(RDyHipOperator op, const double **device_ptr, int64_t *num_values);
 int rdyhip_tracers_get_boundary_fluxes(RDyHipOperator op, int32_t boundary, int32_t num_edges, double *fluxes /* host [num_edges][3+NT] */);
+/* rdyhip_tracers_rhs_function / _euler_step restricted to a phase; flags: RDYHIP_PHASE_RESET_DIAGNOSTICS only
+ * (RDYHIP_PHASE_OVERWRITE is implied and accepted; there is still no accumulate form) */
+int rdyhip_tracer_phase_rhs(RDyHipOperator op, int32_t phase, int32_t flags, double dt, const double *u_local, double *f_global, void *stream);
+int rdyhip_tracer_phase_euler_step(RDyHipOperator op, int32_t phase, int32_t flags, double dt, const double *u_local, double *u_local_out,
+                                   double *f_global /* may be NULL */, void *stream);
+/* ghost update of the [num_cells][3 + NT] state + the evaluation, as rdyhip_rhs_overlapped / rdyhip_euler_step_overlapped */
+int rdyhip_halo_tracers_rhs(RDyHipOperator op, RDyHipHalo halo, double dt, double *u_local, double *f_global, void *stream);
+int rdyhip_halo_tracers_euler_step(RDyHipOperator op, RDyHipHalo halo, double dt, double *u_local, double *u_local_out, double *f_global, void *stream);
 
 /* ---- ensembles: several simulations on one mesh, one launch per evaluation --------------------------------------------------------
  * The reference's `ensemble:` section (docs/common/input.md:158-225, docs/developer/organization.md:373-395; the test deck

@@ -140,6 +140,10 @@ SYMBOLS = {
     "rdyhip_tracers_euler_step": (C.c_int, [_H, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rdyhip_tracers_primitive_variables": (C.c_int, [_H, C.POINTER(C.c_void_p), c_int64_p]),
     "rdyhip_tracers_get_boundary_fluxes": (C.c_int, [_H, C.c_int32, C.c_int32, c_double_p]),
+    "rdyhip_tracer_phase_rhs": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rdyhip_tracer_phase_euler_step": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rdyhip_halo_tracers_rhs": (C.c_int, [_H, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rdyhip_halo_tracers_euler_step": (C.c_int, [_H, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rdyhip_ensemble_enable": (C.c_int, [_H, C.c_int32]),
     "rdyhip_ensemble_info": (C.c_int, [_H, c_int32_p]),
     "rdyhip_ensemble_set_mannings": (C.c_int, [_H, C.c_int32, C.c_int32, c_int32_p, c_double_p]),

@@ -35,7 +35,8 @@ struct RDyHipHalo_s {
   // DMPlexDistributeOverlap, src/rdydm.c:150 -- can put one in a tile no ghost touches): only then may a two-stream step
   // let its launches store send rows while the exchange stream reads the send buffer
   bool            send_cells_in_halo_tiles = true;
-  // The form of a step, per kind of step (0: rdyhip_rhs_overlapped, 1: rdyhip_euler_step_overlapped): everything in order
+  // The form of a step, per kind of step (0: rdyhip_rhs_overlapped, 1: rdyhip_euler_step_overlapped, 2: rdyhip_halo_tracers_rhs,
+  // 3: rdyhip_halo_tracers_euler_step): everything in order
   // on the caller's stream, or the exchange on the library's stream beside the tiles that need no ghost data.  Both forms post
   // the same send / receive group, so every rank chooses for itself: the first 2 x TRIAL steps of a kind alternate between
   // the forms, each timed on the device (events on the caller's stream), and the faster one stays -- on the communicator
@@ -49,7 +50,9 @@ struct RDyHipHalo_s {
     double     ms[2] = {0.0, 0.0};
     int        n[2]  = {0, 0};
     hipEvent_t ev0[2 * TRIAL] = {}, ev1[2 * TRIAL] = {};
-  } choice[2];
+  } choice[4];
+  // the tracer kinds (2, 3) never step on two streams: the pattern receives into owned rows, or the halo has no peers
+  bool            tracers_in_order = false;
   bool            halo_concurrent = true;   // RDYHIP_HALO_CONCURRENT (measurement knob), read at create
   bool            grad_pack_allowed = true; // RDYHIP_GRAD_PACK_FUSED (measurement knob), read at create
   hipStream_t     cs = nullptr;  // exchange stream
@@ -378,7 +381,7 @@ int rdyhip_halo_create(RDyHipOperator op, void *nccl_comm, int32_t npeers, const
         return fail(RDYHIP_ERR_ARG_OUTOFRANGE, "peer rank %d outside the communicator's %d ranks", peers[i], nranks);
       }
   }
-  h->max_comp = op->muscl ? 6 : 3;
+  h->max_comp = std::max(op->muscl ? 6 : 3, op->tracers.n > 0 ? 3 + op->tracers.n : 0);   // tracers enabled later: halo_grow (tracer_calls.h)
   {
     // does an exchange write every ghost row?  (rdyhip_rk4_step then leaves the ghost rows of its stage state to it)
     std::vector<char> got((size_t)op->n_cells, 0);
@@ -429,6 +432,12 @@ int rdyhip_halo_create(RDyHipOperator op, void *nccl_comm, int32_t npeers, const
       if (forced >= 0) {
         c.form   = forced;
         c.source = source;
+      }
+    h->tracers_in_order = source == RDYHIP_HALO_FORM_LOCKED_IN_ORDER || npeers == 0;
+    if (h->tracers_in_order)
+      for (int k = RDYHIP_HALO_STEP_TRACERS_RHS; k <= RDYHIP_HALO_STEP_TRACERS_EULER; ++k) {
+        h->choice[k].form   = 0;
+        h->choice[k].source = RDYHIP_HALO_FORM_LOCKED_IN_ORDER;
       }
     if (const char *e = getenv("RDYHIP_HALO_CONCURRENT")) h->halo_concurrent = atoi(e) != 0;   // measurement knob
     if (const char *e = getenv("RDYHIP_GRAD_PACK_FUSED")) h->grad_pack_allowed = atoi(e) != 0;  // measurement knob
@@ -598,7 +607,7 @@ int32_t rdyhip_halo_overlaps(RDyHipHalo halo) { return halo && halo->choice[0].f
 
 int rdyhip_halo_form_info(RDyHipHalo halo, int32_t kind, RDyHipHaloFormInfo *info) {
   if (!halo || !info) return fail(RDYHIP_ERR_USER, "null argument");
-  if (kind != RDYHIP_HALO_STEP_RHS && kind != RDYHIP_HALO_STEP_EULER) return fail(RDYHIP_ERR_USER, "unknown kind of step %d", kind);
+  if (kind < RDYHIP_HALO_STEP_RHS || kind > RDYHIP_HALO_STEP_TRACERS_EULER) return fail(RDYHIP_ERR_USER, "unknown kind of step %d", kind);
   const RDyHipHalo_s::FormChoice &c = halo->choice[kind];
   info->form          = c.form;
   info->source        = c.source;
@@ -615,8 +624,9 @@ int rdyhip_halo_form_info(RDyHipHalo halo, int32_t kind, RDyHipHaloFormInfo *inf
 
 int rdyhip_halo_set_form(RDyHipHalo halo, int32_t kind, int32_t form) {
   if (!halo) return fail(RDYHIP_ERR_USER, "null halo");
-  if (kind != RDYHIP_HALO_STEP_RHS && kind != RDYHIP_HALO_STEP_EULER) return fail(RDYHIP_ERR_USER, "unknown kind of step %d", kind);
+  if (kind < RDYHIP_HALO_STEP_RHS || kind > RDYHIP_HALO_STEP_TRACERS_EULER) return fail(RDYHIP_ERR_USER, "unknown kind of step %d", kind);
   RDyHipHalo_s::FormChoice &c = halo->choice[kind];
+  if (kind >= RDYHIP_HALO_STEP_TRACERS_RHS && halo->tracers_in_order) return 0;  // stays in order (RDYHIP_HALO_FORM_LOCKED_IN_ORDER)
   if (form < 0) {  // run the trial (again); the events are kept
     c.form = 0;
     c.source = RDYHIP_HALO_FORM_TRIAL_RUNNING;

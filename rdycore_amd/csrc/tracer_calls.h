@@ -33,16 +33,30 @@ int tracers_check(RDyHipOperator op) {
 
 // One tracer evaluation: OperatorRHSFunction's zeroing of F, diagnostics reset and apply in one launch; with u_out the
 // forward-Euler update rides on the stores (f may then be NULL)
-int launch_tracers(RDyHipOperator op, double dt, const double *u, double *f, double *u_out, hipStream_t st) {
+// Phased (rdyhip_tracer_phase_*, the halo steps below): every phase is a launch over ALL owned cells whose threads of the
+// other phase stand aside (tracer_kernels.h), so a workgroup keeps its Courant bucket from phase to phase; reset == 0 merges
+// into the buckets.  A HALO phase on a rank without ghost-adjacent cells launches nothing (with `reset` the buckets are
+// still restarted, as step_two_streams does for the SWE path).
+int launch_tracers(RDyHipOperator op, double dt, const double *u, double *f, double *u_out, hipStream_t st, int32_t phase = RDYHIP_PHASE_ALL,
+                   bool reset = true) {
   if (op->n_owned == 0) return 0;   // a rank may own nothing: nothing to launch
-  op->courant = RDyHipCourant{0.0, -1, -1};
+  if (reset) op->courant = RDyHipCourant{0.0, -1, -1};
+  if (phase == RDYHIP_PHASE_HALO && op->n_halo == 0) {
+    if (reset) {
+      const int rc = rdyhip_reset_diagnostics(op, (void *)st);
+      if (rc) return rc;
+    }
+    op->courant_owned_side = true;
+    return 0;
+  }
   op->courant_owned_side = true;   // rdyhip_update_diagnostics: the cell of a cut edge is the owned one
   KernelArgs a = kernel_args_all_cells(op);
   a.mannings   = op->d_mannings.p;
   a.extsrc     = op->d_extsrc.p;   // the canonical [owned][3] array, whatever the water-only mode of the SWE kernels says
   a.src_mom    = 1;
   a.n_buckets  = (int32_t)op->d_blk_max.n;
-  a.reset_diag = 1;
+  a.reset_diag = reset ? 1 : 0;
+  a.phase      = phase;
   TracerArgs t{};
   t.bvalues = op->tracers.bvalues.p;
   t.bflux   = op->tracers.bflux.p;
@@ -56,7 +70,119 @@ int launch_tracers(RDyHipOperator op, double dt, const double *u, double *f, dou
   return 0;
 }
 
+// what a phased call checks beyond tracers_check: the phase and the flags (RDYHIP_PHASE_OVERWRITE is implied and accepted)
+int tracer_phase_check(int32_t phase, int32_t flags) {
+  if (phase != RDYHIP_PHASE_ALL && phase != RDYHIP_PHASE_INTERIOR && phase != RDYHIP_PHASE_HALO) return fail(RDYHIP_ERR_USER, "unknown phase %d", phase);
+  if (flags & ~(RDYHIP_PHASE_OVERWRITE | RDYHIP_PHASE_RESET_DIAGNOSTICS))
+    return fail(RDYHIP_ERR_USER, "unknown flags %d (the tracer phases take RDYHIP_PHASE_RESET_DIAGNOSTICS only; there is no accumulate form)", flags);
+  return 0;
+}
+
+// ---- the ghost update of the [num_cells][3 + NT] state and the evaluation in one call (rdyhip_halo_tracers_*) --------------
+// A halo created before rdyhip_tracers_enable has buffers of 3 (6) values per cell: the first tracer step makes them
+// 3 + NT wide.  The only place of the tracer path that waits for the device: what the halo's stream and the caller's still
+// run may read the old buffers.  The fused pack's send lists point into d_send and are attached again.
+int halo_grow(RDyHipHalo h, int32_t ncomp, hipStream_t st) {
+  if (ncomp <= h->max_comp) return 0;
+  HIP_TRY(hipStreamSynchronize(h->cs));
+  HIP_TRY(hipStreamSynchronize(st));
+  int rc      = h->d_send.zeros((size_t)h->send_off.back() * ncomp);
+  if (!rc) rc = h->d_recv.zeros((size_t)h->recv_off.back() * ncomp);
+  if (rc) return rc;
+  h->max_comp     = ncomp;
+  h->packed_state = nullptr;
+  if (h->fused_pack && h->op->fused_halo == h) return halo_attach_send_lists(h, true);
+  return 0;
+}
+
+// In order: pack, transfer, unpack of 3 + NT values per cell on the caller's stream, then ONE launch over all owned cells
+int tracer_step_in_order(RDyHipOperator op, RDyHipHalo h, int32_t N, double dt, double *u, double *f, double *u_out, hipStream_t st) {
+  int rc      = halo_pack(h, u, N, st);
+  if (!rc) rc = halo_transfer(h, u, N, st);
+  if (!rc) rc = halo_unpack(h, u, N, st);
+  if (!rc) rc = launch_tracers(op, dt, u, f, u_out, st);
+  return rc;
+}
+
+// Two streams, the simple shape of step_two_streams: the exchange on the halo's stream, the INTERIOR launch (which starts the
+// diagnostic) on the caller's meanwhile -- enqueued before a transport callback that may block the host, behind an
+// asynchronous RCCL group --, the join, then the HALO launch (which merges into the buckets) on the caller's stream too
+int tracer_step_two_streams(RDyHipOperator op, RDyHipHalo h, int32_t N, double dt, double *u, double *f, double *u_out, hipStream_t st) {
+  h->next_events();
+  HIP_TRY(hipEventRecord(h->ev_fork, st));
+  HIP_TRY(hipStreamWaitEvent(h->cs, h->ev_fork, 0));
+  int rc = halo_pack(h, u, N, h->cs);
+  if (!rc && h->transport) rc = launch_tracers(op, dt, u, f, u_out, st, RDYHIP_PHASE_INTERIOR, true);
+  if (!rc) rc = halo_transfer(h, u, N, h->cs);
+  if (!rc) rc = halo_unpack(h, u, N, h->cs);
+  if (!rc && !h->transport) rc = launch_tracers(op, dt, u, f, u_out, st, RDYHIP_PHASE_INTERIOR, true);
+  // an error after the fork still joins the exchange stream back (step_two_streams)
+  hipError_t e = hipEventRecord(h->ev_join, h->cs);
+  if (e == hipSuccess) e = hipStreamWaitEvent(st, h->ev_join, 0);
+  if (rc) return rc;
+  if (e != hipSuccess) return fail(RDYHIP_ERR_LIB, "joining the exchange stream failed: %s", hipGetErrorString(e));
+  return launch_tracers(op, dt, u, f, u_out, st, RDYHIP_PHASE_HALO, false);
+}
+
+// rdyhip_halo_tracers_rhs (euler == false) / rdyhip_halo_tracers_euler_step
+int tracers_overlapped(RDyHipOperator op, RDyHipHalo h, bool euler, double dt, double *u, double *f, double *u_out, hipStream_t st) {
+  int rc = tracers_check(op);
+  if (rc) return rc;
+  if (!h) return fail(RDYHIP_ERR_USER, "null halo");
+  if (h->op != op) return fail(RDYHIP_ERR_USER, "the halo belongs to another operator");
+  if (op->n_cells > 0 && !u) return fail(RDYHIP_ERR_USER, "null u_local");
+  if (euler) {
+    if (u_out == u && u) return fail(RDYHIP_ERR_USER, "rdyhip_halo_tracers_euler_step needs a second state array (not in place)");
+    rc = euler_out_check(op, "rdyhip_halo_tracers_euler_step", u, u_out);
+    if (rc) return rc;
+  } else if (op->n_owned > 0 && !f) {
+    return fail(RDYHIP_ERR_USER, "null f_global");
+  }
+  const int32_t N = 3 + op->tracers.n;
+  rc = halo_grow(h, N, st);
+  if (!rc) rc = halo_check(h, u, N);
+  if (rc) return rc;
+  op->courant            = RDyHipCourant{0.0, -1, -1};
+  op->courant_owned_side = true;
+  const int kind = euler ? RDYHIP_HALO_STEP_TRACERS_EULER : RDYHIP_HALO_STEP_TRACERS_RHS;
+  int       slot = -1;
+  int       form = form_begin(h, kind, st, &slot);
+  if (h->tracers_in_order) form = 0;
+  rc = form ? tracer_step_two_streams(op, h, N, dt, u, f, u_out, st) : tracer_step_in_order(op, h, N, dt, u, f, u_out, st);
+  form_end(h, kind, st, slot);
+  h->packed_state = nullptr;   // d_send holds 3 + NT-wide rows: a later rdyhip_euler_step_overlapped packs again
+  return rc;
+}
+
 }  // namespace
+
+extern "C" int rdyhip_tracer_phase_rhs(RDyHipOperator op, int32_t phase, int32_t flags, double dt, const double *u_local, double *f_global, void *stream) {
+  int rc = tracers_check(op);
+  if (!rc) rc = tracer_phase_check(phase, flags);
+  if (rc) return rc;
+  if (op->n_owned > 0 && (!u_local || !f_global)) return fail(RDYHIP_ERR_USER, "null u_local / f_global");
+  return launch_tracers(op, dt, u_local, f_global, nullptr, (hipStream_t)stream, phase, (flags & RDYHIP_PHASE_RESET_DIAGNOSTICS) != 0);
+}
+
+extern "C" int rdyhip_tracer_phase_euler_step(RDyHipOperator op, int32_t phase, int32_t flags, double dt, const double *u_local, double *u_local_out,
+                                              double *f_global, void *stream) {
+  int rc = tracers_check(op);
+  if (!rc) rc = tracer_phase_check(phase, flags);
+  if (rc) return rc;
+  if (op->n_owned > 0 && !u_local) return fail(RDYHIP_ERR_USER, "null u_local");
+  rc = euler_out_check(op, "rdyhip_tracer_phase_euler_step", u_local, u_local_out);
+  if (rc) return rc;
+  return launch_tracers(op, dt, u_local, f_global, u_local_out, (hipStream_t)stream, phase, (flags & RDYHIP_PHASE_RESET_DIAGNOSTICS) != 0);
+}
+
+extern "C" int rdyhip_halo_tracers_rhs(RDyHipOperator op, RDyHipHalo halo, double dt, double *u_local, double *f_global, void *stream) {
+  return tracers_overlapped(op, halo, false, dt, u_local, f_global, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int rdyhip_halo_tracers_euler_step(RDyHipOperator op, RDyHipHalo halo, double dt, double *u_local, double *u_local_out, double *f_global,
+                                              void *stream) {
+  return tracers_overlapped(op, halo, true, dt, u_local, f_global, u_local_out, (hipStream_t)stream);
+}
 
 extern "C" int rdyhip_tracers_enable(RDyHipOperator op, int32_t num_tracers, int32_t riemann) {
   if (!op) return fail(RDYHIP_ERR_USER, "null operator");

@@ -75,7 +75,11 @@ __device__ __forceinline__ double tracer_roe_flux(const RiemannSide &L, const Ri
 
 // One thread = one owned cell: the cell's own row is prepared once, its up to S slots are walked in slot order, the source
 // epilogue of ApplyTracerSourceSemiImplicit (tracer_petsc.c:617-737) and the stores follow; the Courant bucket goes through
-// block_courant_reduce with the `pos` table, so ties resolve as in swe_rhs_kernel.  PHASE_ALL, f = F(u) only.
+// block_courant_reduce with the `pos` table, so ties resolve as in swe_rhs_kernel.  f = F(u) only.
+// Phases (KernelArgs::phase, a run-time scalar: no further instantiations): every launch has one thread per owned cell, and a
+// thread whose cell is not of the launch's phase -- ghost adjacency is the NBR_GHOST bit of its neighbour ids, as in
+// swe_rhs_kernel -- loads and stores nothing and enters the reduction with best = 0.  A workgroup therefore has the same
+// Courant bucket in every phase, and a launch with reset_diag == 0 merges into it (block_courant_reduce).
 template <int S, int NT, bool UPWIND>
 __global__ __launch_bounds__(BLOCK) void tracer_rhs_kernel(const KernelArgs a, const TracerArgs t, const double dt, const double *__restrict__ u) {
   constexpr int N = 3 + NT;
@@ -85,14 +89,24 @@ __global__ __launch_bounds__(BLOCK) void tracer_rhs_kernel(const KernelArgs a, c
   int    best_slot = -1;
   int    o         = 0;
 
-  const bool active = i < a.n_work;
+  bool           active = i < a.n_work;
+  int32_t        id[S];
+  const int32_t *nbr = RDY_COLD(a, nbr);
   if (active) {
-    o = i;
-    const int32_t *nbr = RDY_COLD(a, nbr), *btype = RDY_COLD(a, btype);
-    const double  *cn_ = RDY_COLD(a, cn), *sn_ = RDY_COLD(a, sn);
-    int32_t        id[S];
+    o              = i;
+    bool has_ghost = false;
 #pragma unroll
-    for (int s = 0; s < S; ++s) id[s] = nbr[s * a.stride + o];
+    for (int s = 0; s < S; ++s) {
+      id[s] = nbr[s * a.stride + o];
+      has_ghost |= (id[s] >= 0) && (id[s] & NBR_GHOST);
+    }
+    // a cell of the other phase: nothing but its neighbour ids is loaded, nothing is stored (a.phase is uniform per launch)
+    if (a.phase == RDYHIP_PHASE_INTERIOR && has_ghost) active = false;
+    if (a.phase == RDYHIP_PHASE_HALO && !has_ghost) active = false;
+  }
+  if (active) {
+    const int32_t *btype = RDY_COLD(a, btype);
+    const double  *cn_ = RDY_COLD(a, cn), *sn_ = RDY_COLD(a, sn);
 
     const int64_t c = a.o2l ? a.o2l[o] : o;
     double        own[N];

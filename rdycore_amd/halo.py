@@ -157,17 +157,19 @@ class HaloExchange:
         return bool(lib.rdyhip_halo_pack_fused(self._halo))
 
     FORM_SOURCES = ("trial_running", "measured", "forced", "default", "locked_in_order")
+    STEP_KINDS = {"rhs": 0, "euler": 1, "tracers_rhs": 2, "tracers_euler": 3}     # RDYHIP_HALO_STEP_*
 
     def form_info(self, kind: str = "rhs") -> dict:
         """rdyhip_halo_form_info: which form the steps of this halo take (in order on the caller's stream / two streams) and why:
         the library times both forms over the first 16 calls of a kind ("rhs": rhs_overlapped, "euler": step_overlapped) on the
-        communicator it really has and keeps the faster one"""
+        communicator it really has and keeps the faster one; "tracers_rhs" / "tracers_euler": tracers_rhs_overlapped /
+        tracers_step_overlapped, which stay in order ("locked_in_order") on a halo without peers"""
         import ctypes as C
         from . import _lib
         if self._halo is None:
             return {"form": "none", "source": "no_halo"}
         info = _lib.RDyHipHaloFormInfo()
-        _lib.check(_lib.load().rdyhip_halo_form_info(self._halo, 1 if kind == "euler" else 0, C.byref(info)))
+        _lib.check(_lib.load().rdyhip_halo_form_info(self._halo, self.STEP_KINDS[kind], C.byref(info)))
         return {"form": "two_streams" if info.form else "in_order", "source": self.FORM_SOURCES[info.source], "trial_steps": int(info.trial_steps),
                 "in_order_ms": float(info.in_order_ms), "two_stream_ms": float(info.two_stream_ms)}
 
@@ -176,7 +178,7 @@ class HaloExchange:
         from . import _lib
         if self._halo is not None:
             f = -1 if form is None else (1 if form in (1, True, "two_streams") else 0)
-            _lib.check(_lib.load().rdyhip_halo_set_form(self._halo, 1 if kind == "euler" else 0, f))
+            _lib.check(_lib.load().rdyhip_halo_set_form(self._halo, self.STEP_KINDS[kind], f))
 
     def invalidate(self):
         """the state array was written by somebody else since the last step: the next step packs again"""
@@ -448,6 +450,35 @@ class HaloExchange:
         """u_out[owned] = u_local[owned] + dt RHS(u_local) (Operator.euler_step) with the ghost update of u_local
         overlapped the same way; the ghost rows of u_out are filled by the next call's exchange."""
         self._overlapped(op, dt, u_local, None, u_out)
+
+    # -- the same for the [num_cells, 3 + NT] state of an operator with tracers (transport="c" only) -----------------
+    def tracers_rhs_overlapped(self, op, dt: float, u_local: torch.Tensor, f_global: torch.Tensor):
+        """rdyhip_halo_tracers_rhs: the ghost update of u_local [num_cells, 3 + NT] and Operator.tracers_rhs_function in one
+        call, in order or on two streams as the halo's trial of this kind of step decides"""
+        self._tracers_overlapped(op, dt, u_local, f_global, None)
+
+    def tracers_step_overlapped(self, op, dt: float, u_local: torch.Tensor, u_out: torch.Tensor, f_global: Optional[torch.Tensor] = None):
+        """rdyhip_halo_tracers_euler_step: the ghost update of u_local and Operator.tracers_euler_step; the ghost rows of
+        u_out are filled by the next call's exchange"""
+        self._tracers_overlapped(op, dt, u_local, f_global, u_out)
+
+    def _tracers_overlapped(self, op, dt, u_local, f_global, u_out):
+        if self.world == 1:
+            if u_out is not None:
+                op.tracers_euler_step(dt, u_local, u_out, f_global)
+            else:
+                op.tracers_rhs_function(dt, u_local, f_global)
+            return
+        if self._halo is None:
+            raise ValueError('the tracer steps go through the halo behind the C ABI: HaloExchange(..., transport="c", op=op)')
+        from . import _lib
+        lib = _lib.load()
+        st = int(torch.cuda.current_stream(self.device).cuda_stream)
+        f = int(f_global.data_ptr()) if f_global is not None else None
+        if u_out is not None:
+            _lib.check(lib.rdyhip_halo_tracers_euler_step(op._h, self._halo, float(dt), int(u_local.data_ptr()), int(u_out.data_ptr()), f, st))
+        else:
+            _lib.check(lib.rdyhip_halo_tracers_rhs(op._h, self._halo, float(dt), int(u_local.data_ptr()), f, st))
 
     def _overlapped(self, op, dt, u_local, f_global, u_out):
         def part(phase, reset=False, ready=False):

@@ -470,6 +470,24 @@ class Operator:
         _lib.check(_lib.load().rdyhip_tracers_euler_step(self._h, float(dt), _ptr(u_local), _ptr(u_out),
                                                          _ptr(f_global) if f_global is not None else None, _stream()))
 
+    def tracers_rhs_phase(self, phase: int, dt: float, u_local: torch.Tensor, f_global: torch.Tensor, reset_diagnostics: bool = False):
+        """rdyhip_tracer_phase_rhs: tracers_rhs_function for the owned cells of one phase (0: all, 1: without a ghost neighbour,
+        2: with one); rows of the other phase are not touched.  reset_diagnostics=False merges into the Courant diagnostic"""
+        self._check_tracer_state(u_local, "u_local", self.mesh.num_cells)
+        self._check_tracer_state(f_global, "f_global", self.mesh.num_owned_cells)
+        _lib.check(_lib.load().rdyhip_tracer_phase_rhs(self._h, int(phase), 2 if reset_diagnostics else 0, float(dt), _ptr(u_local), _ptr(f_global),
+                                                       _stream()))
+
+    def tracers_euler_step_phase(self, phase: int, dt: float, u_local: torch.Tensor, u_out: torch.Tensor, f_global: Optional[torch.Tensor] = None,
+                                 reset_diagnostics: bool = False):
+        """rdyhip_tracer_phase_euler_step: tracers_euler_step for the owned cells of one phase, each phase writing its own rows of
+        u_out"""
+        self._check_tracer_state(u_local, "u_local", self.mesh.num_cells)
+        self._check_tracer_state(u_out, "u_out", self.mesh.num_cells)
+        self._check_tracer_state(f_global, "f_global", self.mesh.num_owned_cells, optional=True)
+        _lib.check(_lib.load().rdyhip_tracer_phase_euler_step(self._h, int(phase), 2 if reset_diagnostics else 0, float(dt), _ptr(u_local), _ptr(u_out),
+                                                              _ptr(f_global) if f_global is not None else None, _stream()))
+
     def tracers_primitive_variables(self) -> torch.Tensor:
         """rdyhip_tracers_primitive_variables: [owned, 3 + NT] (h, u, v, c_0 ...) as a view of the device array; stored by every
         tracer evaluation after the first request, zeros until one has run"""

@@ -330,3 +330,41 @@ class EnsembleEulerStepper:
             self.times = self.times + d
             self.step += 1
         return cur
+
+
+class TracerEulerStepper:
+    """Forward Euler for an operator with tracers enabled (Operator.enable_tracers): fused Euler steps
+    (rdyhip_tracers_euler_step: the update rides on the kernel's stores) ping-ponging between two [num_cells, 3 + NT] arrays.
+    With a `halo` (HaloExchange, transport="c") every step is HaloExchange.tracers_step_overlapped -- the ghost update of the
+    3 + NT-wide state and the step in one call -- so only the owned rows of the arrays need to be current between steps."""
+
+    def __init__(self, op, halo=None):
+        self.op = op
+        self.halo = halo
+        self.step = 0
+        self.time = 0.0
+        self._own = [None, None]  # the stepper's arrays: the partner of the caller's array, and the partner of that one
+
+    def _partner(self, u: torch.Tensor) -> torch.Tensor:
+        """as EnsembleEulerStepper._partner: never `u`, never another array of the caller's"""
+        k = 1 if self._own[0] is u else 0
+        a = self._own[k]
+        if a is None or a.shape != u.shape or a.device != u.device:
+            a = self._own[k] = u.clone()     # ghost rows start as u's
+        return a
+
+    def advance(self, u: torch.Tensor, dt: float, nsteps: int) -> torch.Tensor:
+        """`nsteps` steps of `dt` from `u`; returns the array that holds the result: `u` after an even number of steps, else one
+        of the stepper's own two arrays (a later advance overwrites it), which may be handed back as the next `u`.  The caller
+        sets sources and boundary values between calls.  With a halo the ghost rows of the returned array are one step old
+        (or the caller's): the next step's exchange fills them."""
+        cur, nxt = u, self._partner(u)
+        for _ in range(int(nsteps)):
+            if self.halo is not None:
+                self.halo.tracers_step_overlapped(self.op, dt, cur, nxt)
+            else:
+                self.op.tracers_euler_step(dt, cur, nxt)
+            cur, nxt = nxt, cur
+            self.time += dt
+            self.step += 1
+        return cur
