@@ -841,8 +841,8 @@ int rdyhip_error_sums_get(RDyHipOperator op, RDyHipErrorSums *out);
  *   ghosts, and the len / area of a ghost that is the smaller cell of a cut edge, do not enter; the cell reported for a cut edge
  *   is the owned one.  The maximum over the ranks is still the whole mesh's: the smaller cell of every cut edge is owned by someone.
  * Ghost rows of 3 + NT values travel through the halo object (rdyhip_halo_tracers_* below, rdyhip_halo_exchange with
- * ncomp = 3 + NT) or through rdyhip_pack_rows / rdyhip_unpack_rows; the output means, the time series and the read-out cover
- * the three flow components of the SWE state only.
+ * ncomp = 3 + NT) or through rdyhip_pack_rows / rdyhip_unpack_rows; rdyhip_output_mean_*, rdyhip_series_* and rdyhip_state_* cover
+ * the three flow components of the SWE state only: the 3 + NT-wide forms are "tracer output" below.
  *
  * On several ranks (a partitioned mesh; DMGlobalToLocalBegin/End of OperatorRHSFunction, src/rdysetup.c:1133-1134, ahead of
  * the tracer operators of src/tracer/tracer_petsc.c):
@@ -889,6 +889,79 @@ int rdyhip_tracer_phase_euler_step(RDyHipOperator op, int32_t phase, int32_t fla
 /* ghost update of the [num_cells][3 + NT] state + the evaluation, as rdyhip_rhs_overlapped / rdyhip_euler_step_overlapped */
 int rdyhip_halo_tracers_rhs(RDyHipOperator op, RDyHipHalo halo, double dt, double *u_local, double *f_global, void *stream);
 int rdyhip_halo_tracers_euler_step(RDyHipOperator op, RDyHipHalo halo, double dt, double *u_local, double *u_local_out, double *f_global, void *stream);
+
+/* ---- tracer output: read-out, error sums, output means and observation series of the [num_cells][3 + NT] state ----------------
+ * What the three sections "time-averaged output fields", "time series on the device" and "state read-out" above do for rows of
+ * three doubles, for the tracer state's rows of N = 3 + NT (csrc/tracer_output_kernels.h), so that a sediment run needs no copy of
+ * the whole state to the host for a concentration field, an MMS norm, an averaged output or a gauge record.  The reference treats
+ * none of these as flow-only:
+ *   rdyhip_tracer_state_planes / _read_*   RDyGetOwnedCell* of src/rdydata.c:171-205 for any component of the n_dof-wide Vec, and
+ *                                          the XDMF output variables, Vecs of block size n_dof (src/xdmf_output.c:196-241)
+ *   rdyhip_tracer_error_sums / _get        the rank-local loops of RDyMMSComputeErrorNorms over ndof (src/rdymms.c:859-880)
+ *   rdyhip_tracer_output_mean_*            AccumulateOutputVar / ComputeMean / ResetOutputVar (src/xdmf_output.c:196-241, 436-504)
+ *   rdyhip_tracer_series_*                 WriteObservations with num_comp columns per site (src/time_series.c:419-440)
+ * The entry points carry the prefix rdyhip_tracer_ (as rdyhip_tracer_phase_*), not rdyhip_tracers_: that prefix names the eight
+ * calls of the evaluation itself.  Every call reports a null operator first, "tracers are not enabled" next, and every other
+ * argument error before any device call, all as RDYHIP_ERR_USER; on a rank that owns nothing it launches nothing while times
+ * and record counts still advance; owned cells that are not the first rows of the local vector are found through the operator's
+ * own table.  All device memory is counted in RDyHipLayoutInfo.device_bytes and freed by rdyhip_destroy, after a copy in flight.
+ *
+ * `comps` is a mask: bit i stands for component i of the row, 0 <= i < N (bits 0..2 are RDYHIP_COMPONENT_H / _HU / _HV, bit 3 + j
+ * is tracer j).  An empty mask or a bit at N or above: RDYHIP_ERR_USER.  `comp` is exactly one bit.  `form`:
+ *   RDYHIP_TRACER_FORM_CONSERVED  (h, hu, hv, h c_0 ...): the row as it is.  Nothing is computed, values move as 64-bit patterns:
+ *                                 -0.0, NaN payloads and denormals survive.
+ *   RDYHIP_TRACER_FORM_PRIMITIVE  (h, u, v, c_0 ...): what a tracer evaluation stores as primitive variables
+ *                                 (rdyhip_tracers_primitive_variables), with that store's own arithmetic -- the same bits.
+ *   - rdyhip_tracer_state_planes, the device form: ONE launch on `stream`.  d_planes[k][o] = row(loc(o))[c_k], k over the set bits
+ *     c_k of `comps` ascending, o over the owned cells; d_planes is device memory [popcount(comps)][num_owned_cells].
+ *   - rdyhip_tracer_state_read_begin / _ready / _wait / _get / _ptr: the state machine of rdyhip_state_read_* word for word --
+ *     the launch on `stream`, an event, the copy into pinned memory on the operator's copy stream, a second event; only _wait
+ *     blocks; a begin over a read in flight is ordered behind the earlier copy and replaces it; size != num_owned_cells is
+ *     RDYHIP_ERR_ARG_SIZ -- with planes, pinned memory and events of its own: a flow read and a tracer read may be in flight at
+ *     once and neither disturbs the other.
+ *   - rdyhip_tracer_error_sums / _get: rdyhip_error_sums for N components; d_exact is device memory [num_owned_cells][N] or NULL.
+ *     The same two launches without atomics, the same block size, workgroup count, lane-to-cell assignment and order of every
+ *     addition, with records of 3 N + 1 doubles: components 0..2 are the SAME BITS rdyhip_error_sums gives for the [cell][3] slice
+ *     of the same state, and a tracer column equal to the h column gives the h column's bits.  Entries at N and above are 0.  The
+ *     area table is shared with rdyhip_error_sums; records and the pinned result are this feature's.  _get is the only blocking
+ *     call.  The MPI_Allreduce and the square root stay with the caller.
+ *   - rdyhip_tracer_output_mean_*: three accumulators [num_owned_cells][N] (`vars`: RDYHIP_OUTPUT_* bits), each with its own time.
+ *     _accumulate is one launch for any subset: the solution fma(dt, u_solution[loc(o)], acc); the primitive variables formed in
+ *     the launch from u_primitive[loc(o)] with the FORM_PRIMITIVE arithmetic -- there is no hidden "state of the last
+ *     evaluation": the caller passes the array the reference's source operator saw, the input of a fused Euler step or the
+ *     argument of a plain evaluation; where the two pointers are equal the row is read once; either may be NULL when its variable
+ *     is not in `vars` --; the sources, row = the operator's [owned][3] external source followed by the [owned][NT] tracer source,
+ *     read at the call's place in `stream` exactly as rdyhip_output_mean_accumulate documents (the water-only plane and the
+ *     uniform-source mode of the SWE kernels change nothing: the canonical arrays are always current).  _get scales by 1 / time
+ *     formed on the host into d_mean (device, [num_owned_cells][N]); no accumulated time: RDYHIP_ERR_USER.  A second _enable
+ *     keeps an accumulator's content.
+ *   - rdyhip_tracer_series_*: the semantics of RDYHIP_SERIES_OBSERVATIONS with N values per site -- sites are owned-cell ids,
+ *     range-checked on the host; repeats are allowed; num_sites == 0 is valid; a full log is RDYHIP_ERR_USER with nothing
+ *     launched; a second enable is RDYHIP_ERR_USER; _read (host arrays, values [count][num_sites][N]) is the only blocking call.
+ *     There is no boundary-flux series for tracers: the reference refuses it (src/time_series.c:76-78, ndof == 3 only). */
+#define RDYHIP_TRACER_FORM_CONSERVED 0
+#define RDYHIP_TRACER_FORM_PRIMITIVE 1
+typedef struct {
+  double l1[10], l2_squared[10], linf[10], area;   /* entries >= 3 + NT are 0 */
+} RDyHipTracerErrorSums;
+int rdyhip_tracer_state_planes(RDyHipOperator op, int32_t comps, int32_t form, const double *u_local, double *d_planes, void *stream);
+int rdyhip_tracer_state_read_begin(RDyHipOperator op, int32_t comps, int32_t form, const double *u_local, void *stream);
+int rdyhip_tracer_state_read_ready(RDyHipOperator op, int32_t *ready);
+int rdyhip_tracer_state_read_wait(RDyHipOperator op);
+int rdyhip_tracer_state_read_get(RDyHipOperator op, int32_t comp, int32_t size, double *values /* host */);
+int rdyhip_tracer_state_read_ptr(RDyHipOperator op, int32_t comp, const double **pinned_values);
+int rdyhip_tracer_error_sums(RDyHipOperator op, const double *u_local, const double *d_exact /* [owned][N] or NULL */, void *stream);
+int rdyhip_tracer_error_sums_get(RDyHipOperator op, RDyHipTracerErrorSums *out);
+int rdyhip_tracer_output_mean_enable(RDyHipOperator op, int32_t vars);
+int rdyhip_tracer_output_mean_accumulate(RDyHipOperator op, int32_t vars, double dt, const double *u_solution, const double *u_primitive, void *stream);
+int rdyhip_tracer_output_mean_get(RDyHipOperator op, int32_t var, double *d_mean /* [owned][N] */, double *accumulated_time, void *stream);
+int rdyhip_tracer_output_mean_reset(RDyHipOperator op, int32_t vars, void *stream);
+int rdyhip_tracer_output_mean_time(RDyHipOperator op, int32_t var, double *accumulated_time);
+int rdyhip_tracer_series_enable(RDyHipOperator op, int32_t num_sites, const int32_t *owned_cell_ids /* host */, int32_t capacity);
+int rdyhip_tracer_series_record(RDyHipOperator op, double time, const double *u_local, void *stream);
+int rdyhip_tracer_series_info(RDyHipOperator op, int32_t *entries, int32_t *count, int32_t *capacity);
+int rdyhip_tracer_series_read(RDyHipOperator op, int32_t first, int32_t count, double *times, double *values /* host [count][S][N] */, void *stream);
+int rdyhip_tracer_series_clear(RDyHipOperator op);
 
 /* ---- ensembles: several simulations on one mesh, one launch per evaluation --------------------------------------------------------
  * The reference's `ensemble:` section (docs/common/input.md:158-225, docs/developer/organization.md:373-395; the test deck

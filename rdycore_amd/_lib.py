@@ -61,6 +61,10 @@ class RDyHipErrorSums(C.Structure):
     _fields_ = [("l1", C.c_double * 3), ("l2_squared", C.c_double * 3), ("linf", C.c_double * 3), ("area", C.c_double)]
 
 
+class RDyHipTracerErrorSums(C.Structure):
+    _fields_ = [("l1", C.c_double * 10), ("l2_squared", C.c_double * 10), ("linf", C.c_double * 10), ("area", C.c_double)]
+
+
 # every symbol include/rdyhip.h declares: name -> (restype, argtypes)
 _H = C.c_void_p  # RDyHipOperator
 SYMBOLS = {
@@ -144,6 +148,24 @@ SYMBOLS = {
     "rdyhip_tracer_phase_euler_step": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rdyhip_halo_tracers_rhs": (C.c_int, [_H, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rdyhip_halo_tracers_euler_step": (C.c_int, [_H, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rdyhip_tracer_state_planes": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rdyhip_tracer_state_read_begin": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "rdyhip_tracer_state_read_ready": (C.c_int, [_H, c_int32_p]),
+    "rdyhip_tracer_state_read_wait": (C.c_int, [_H]),
+    "rdyhip_tracer_state_read_get": (C.c_int, [_H, C.c_int32, C.c_int32, c_double_p]),
+    "rdyhip_tracer_state_read_ptr": (C.c_int, [_H, C.c_int32, C.POINTER(c_double_p)]),
+    "rdyhip_tracer_error_sums": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rdyhip_tracer_error_sums_get": (C.c_int, [_H, C.POINTER(RDyHipTracerErrorSums)]),
+    "rdyhip_tracer_output_mean_enable": (C.c_int, [_H, C.c_int32]),
+    "rdyhip_tracer_output_mean_accumulate": (C.c_int, [_H, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rdyhip_tracer_output_mean_get": (C.c_int, [_H, C.c_int32, C.c_void_p, c_double_p, C.c_void_p]),
+    "rdyhip_tracer_output_mean_reset": (C.c_int, [_H, C.c_int32, C.c_void_p]),
+    "rdyhip_tracer_output_mean_time": (C.c_int, [_H, C.c_int32, c_double_p]),
+    "rdyhip_tracer_series_enable": (C.c_int, [_H, C.c_int32, c_int32_p, C.c_int32]),
+    "rdyhip_tracer_series_record": (C.c_int, [_H, C.c_double, C.c_void_p, C.c_void_p]),
+    "rdyhip_tracer_series_info": (C.c_int, [_H, c_int32_p, c_int32_p, c_int32_p]),
+    "rdyhip_tracer_series_read": (C.c_int, [_H, C.c_int32, C.c_int32, c_double_p, c_double_p, C.c_void_p]),
+    "rdyhip_tracer_series_clear": (C.c_int, [_H]),
     "rdyhip_ensemble_enable": (C.c_int, [_H, C.c_int32]),
     "rdyhip_ensemble_info": (C.c_int, [_H, c_int32_p]),
     "rdyhip_ensemble_set_mannings": (C.c_int, [_H, C.c_int32, C.c_int32, c_int32_p, c_double_p]),

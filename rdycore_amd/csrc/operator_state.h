@@ -194,6 +194,50 @@ struct TracerState {
   size_t bytes() const { return bvalues.bytes() + bflux.bytes() + src.bytes() + pv.bytes(); }
 };
 
+// rdyhip_tracer_state_* / _error_sums / _output_mean_* / _series_* (tracer_output_kernels.h): the read-out, the error sums, the
+// output means and the observation series of the [cell][N = 3 + NT] state, each a copy of what Readout, OutputMeans and Series
+// hold for rows of three -- of their own, so that a flow read and a tracer read may be in flight together.  The area table of
+// the error sums is Readout::d_area.  Everything is allocated by the first call that needs it (means, series: by their enable).
+struct TracerOutput {
+  enum State { NONE, IN_FLIGHT, LANDED };
+  // the getters
+  DevBuf<double> d_planes;            // [popcount(comps)][n_owned], room for the widest mask asked for so far
+  double        *h_planes = nullptr;  // pinned, as many doubles as d_planes
+  size_t         h_cap = 0;
+  hipEvent_t     launched = nullptr, done = nullptr;
+  State          state = NONE;
+  int32_t        comps = 0;           // the mask of the last begin
+  // the error sums
+  DevBuf<double> d_records;           // [err_wg + 1][3 N + 1]: the workgroups' records, then the result
+  double        *h_sums = nullptr;    // pinned, 3 N + 1 doubles
+  hipEvent_t     sums_done = nullptr;
+  State          sums_state = NONE;
+  // the output means: one [n_owned][N] accumulator per enabled variable and the time it spans
+  DevBuf<double> acc[3];
+  double         time[3] = {0.0, 0.0, 0.0};
+  // the observation series: `capacity` records of entries x N doubles, the time of every record on the host
+  bool                series_enabled = false;
+  int32_t             entries = 0, capacity = 0;
+  DevBuf<double>      d_log;
+  DevBuf<int32_t>     d_sites;        // [entries] local cell of every site
+  std::vector<double> times;          // size() = the number of records
+  TracerOutput() = default;
+  TracerOutput(const TracerOutput &) = delete;
+  TracerOutput &operator=(const TracerOutput &) = delete;
+  ~TracerOutput() {
+    if (state == IN_FLIGHT && done) (void)hipEventSynchronize(done);   // the copies write pinned memory
+    if (sums_state == IN_FLIGHT && sums_done) (void)hipEventSynchronize(sums_done);
+    if (h_planes) (void)hipHostFree(h_planes);
+    if (h_sums) (void)hipHostFree(h_sums);
+    if (launched) (void)hipEventDestroy(launched);
+    if (done) (void)hipEventDestroy(done);
+    if (sums_done) (void)hipEventDestroy(sums_done);
+  }
+  size_t bytes() const {
+    return d_planes.bytes() + d_records.bytes() + acc[0].bytes() + acc[1].bytes() + acc[2].bytes() + d_log.bytes() + d_sites.bytes();
+  }
+};
+
 // rdyhip_ensemble_* (ensemble_kernels.h): B members on this operator's mesh, all allocated by rdyhip_ensemble_enable.  The
 // launch is (grid, groups) workgroups, every group walking per_group members (the last one maybe fewer).
 struct EnsembleState {
@@ -295,12 +339,14 @@ struct RDyHipOperator_s : LayoutCounts {
   Series        series[2];   // 0: observations, 1: boundary fluxes
   Readout       readout;
   TracerState   tracers;
+  TracerOutput  tracer_out;
   EnsembleState ensemble;
   DiagnosticsRead diag_read[2];   // RDYHIP_DIAGNOSTICS_OPERATOR, RDYHIP_DIAGNOSTICS_ENSEMBLE
 
   int64_t device_bytes = 0;   // what rdyhip_create allocated; rdyhip_layout_info adds the features'
   int64_t feature_bytes() const {
-    return (int64_t)(rk4.bytes() + means.bytes() + series[0].bytes() + series[1].bytes() + readout.bytes() + tracers.bytes() + ensemble.bytes());
+    return (int64_t)(rk4.bytes() + means.bytes() + series[0].bytes() + series[1].bytes() + readout.bytes() + tracers.bytes() + tracer_out.bytes() +
+                     ensemble.bytes());
   }
 };
 

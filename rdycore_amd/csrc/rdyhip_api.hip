@@ -1,7 +1,7 @@
 // MI355X-native SWE right-hand-side operator: the one translation unit of the library.  Here: create / destroy, the launch
 // selection and the thin entry points of the C ABI declared in include/rdyhip.h; the mesh repack is host_layout.h, the
 // operator's state operator_state.h, the setters field_io.h, the ghost exchange halo_*.h, and every feature on top of the RHS
-// (RK4, output means, time series, read-out, tracers, ensembles) its own *_calls.h.  gfx950 only.
+// (RK4, output means, time series, read-out, tracers and their output, ensembles) its own *_calls.h.  gfx950 only.
 //
 // Layout (built by host_layout.h): one thread owns one owned cell.  The cell's
 // edges are stored as up to S "slots" (S = 3 for triangle meshes, 4 when
@@ -48,6 +48,7 @@
 #include "series_kernels.h"
 #include "readout_kernels.h"
 #include "tracer_kernels.h"
+#include "tracer_output_kernels.h"
 #include "ensemble_kernels.h"
 #include "operator_state.h"
 
@@ -796,6 +797,7 @@ int rdyhip_layout_info(RDyHipOperator op, RDyHipLayoutInfo *info) {
 #include "series_calls.h"
 #include "readout_calls.h"
 #include "tracer_calls.h"
+#include "tracer_output_calls.h"
 #include "ensemble_calls.h"
 #include "diagnostics_calls.h"
 

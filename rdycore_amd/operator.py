@@ -33,6 +33,7 @@ SERIES_OBSERVATIONS, SERIES_BOUNDARY_FLUXES = 1, 2                      # RDYHIP
 COMPONENT_H, COMPONENT_HU, COMPONENT_HV = 1, 2, 4                       # RDYHIP_COMPONENT_*: the planes of the state read-out
 MAX_TRACERS = 7                                                         # RDYHIP_MAX_TRACERS
 TRACER_RIEMANN_ROE, TRACER_RIEMANN_UPWIND_ROE = 0, 1                    # RDYHIP_TRACER_RIEMANN_*
+TRACER_FORM_CONSERVED, TRACER_FORM_PRIMITIVE = 0, 1                     # RDYHIP_TRACER_FORM_*: the rows of the tracer read-out
 DIAGNOSTICS_OPERATOR, DIAGNOSTICS_ENSEMBLE = 0, 1                       # RDYHIP_DIAGNOSTICS_*: the scopes of the non-blocking read-back
 
 
@@ -505,6 +506,125 @@ class Operator:
         out = np.zeros((n, 3 + self.num_tracers))
         _lib.check(_lib.load().rdyhip_tracers_get_boundary_fluxes(self._h, int(boundary), n, out.ctypes.data_as(_lib.c_double_p) if out.size else None))
         return out
+
+    # -- tracer output (rdyhip_tracer_state_* / _error_sums / _output_mean_* / _series_*): the read-out, error sums, output means
+    # and observation series of the [num_cells, 3 + NT] state; `comps`: bit i = component i of the row --------------------------
+    def _tracer_mask_bits(self, comps: int) -> int:
+        n = 3 + self.num_tracers
+        return bin(int(comps)).count("1") if 1 <= int(comps) < (1 << n) else 0
+
+    def tracers_state_planes(self, u_local: torch.Tensor, comps: int, form: int = TRACER_FORM_CONSERVED,
+                             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """rdyhip_tracer_state_planes: [popcount(comps), owned] device tensor, plane k = the k-th component in `comps`
+        (ascending) of the owned cells' rows -- TRACER_FORM_CONSERVED: bit for bit; TRACER_FORM_PRIMITIVE: (h, u, v, c_0 ...) as a
+        tracer evaluation stores them; one launch on the current stream.  `out`: as Operator.state_planes."""
+        self._check_tracer_state(u_local, "u_local", self.mesh.num_cells)
+        k, no = self._tracer_mask_bits(comps), self.mesh.num_owned_cells
+        if out is None:
+            out = torch.empty((k, no), dtype=torch.float64, device="cuda")
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() >= k * no):
+            raise RDyHipError(83, f"out must be a contiguous float64 device tensor of at least {k} x {no} values")
+        _lib.check(_lib.load().rdyhip_tracer_state_planes(self._h, int(comps), int(form), _ptr(u_local), _ptr(out), _stream()))
+        return out
+
+    def tracers_read_state_begin(self, u_local: torch.Tensor, comps: int, form: int = TRACER_FORM_CONSERVED):
+        """rdyhip_tracer_state_read_begin: as read_state_begin, for the tracer state, with buffers of its own"""
+        self._check_tracer_state(u_local, "u_local", self.mesh.num_cells)
+        _lib.check(_lib.load().rdyhip_tracer_state_read_begin(self._h, int(comps), int(form), _ptr(u_local), _stream()))
+
+    def tracers_read_state_ready(self) -> bool:
+        """rdyhip_tracer_state_read_ready: the copy of the last tracers_read_state_begin has finished (an event query)"""
+        out = C.c_int32()
+        _lib.check(_lib.load().rdyhip_tracer_state_read_ready(self._h, C.byref(out)))
+        return bool(out.value)
+
+    def tracers_read_state(self, comp: int) -> np.ndarray:
+        """rdyhip_tracer_state_read_wait + _get: waits for the copy of the last tracers_read_state_begin (for that alone) and
+        returns component `comp` (exactly one bit) of the owned cells as a numpy array"""
+        lib = _lib.load()
+        _lib.check(lib.rdyhip_tracer_state_read_wait(self._h))
+        out = np.empty(self.mesh.num_owned_cells)
+        _lib.check(lib.rdyhip_tracer_state_read_get(self._h, int(comp), int(out.size), out.ctypes.data_as(_lib.c_double_p) if out.size else None))
+        return out
+
+    def tracers_error_sums(self, u_local: torch.Tensor, exact: Optional[torch.Tensor] = None) -> dict:
+        """rdyhip_tracer_error_sums + _get: {"l1", "l2_squared", "linf": [3 + NT] arrays, "area": float} of u_local - exact over
+        the owned cells of this rank (`exact`: [owned, 3 + NT] device tensor; None: zeros); the flow columns are the bits of
+        error_sums for the [cell, 3] slice.  The reduction over ranks and the square root are the caller's."""
+        self._check_tracer_state(u_local, "u_local", self.mesh.num_cells)
+        self._check_tracer_state(exact, "exact", self.mesh.num_owned_cells, optional=True)
+        lib = _lib.load()
+        _lib.check(lib.rdyhip_tracer_error_sums(self._h, _ptr(u_local), _ptr(exact) if exact is not None else None, _stream()))
+        s = _lib.RDyHipTracerErrorSums()
+        _lib.check(lib.rdyhip_tracer_error_sums_get(self._h, C.byref(s)))
+        n = 3 + self.num_tracers
+        return {"l1": np.array(s.l1[:n]), "l2_squared": np.array(s.l2_squared[:n]), "linf": np.array(s.linf[:n]), "area": float(s.area),
+                "padding": np.array(s.l1[n:] + s.l2_squared[n:] + s.linf[n:])}
+
+    def tracers_enable_output_means(self, vars: int):
+        """rdyhip_tracer_output_mean_enable: a zeroed [owned, 3 + NT] accumulator for each of OUTPUT_* in `vars` that has none yet"""
+        _lib.check(_lib.load().rdyhip_tracer_output_mean_enable(self._h, int(vars)))
+
+    def tracers_accumulate_output_means(self, vars: int, dt: float, u_solution: Optional[torch.Tensor] = None,
+                                        u_primitive: Optional[torch.Tensor] = None):
+        """rdyhip_tracer_output_mean_accumulate: all of `vars` in one launch on the current stream -- the solution from
+        `u_solution`, the primitive variables formed from `u_primitive` (the state the evaluation saw: after a fused Euler step
+        its input), the sources from the operator's arrays; each state [num_cells, 3 + NT], needed only with its variable"""
+        self._check_tracer_state(u_solution, "u_solution", self.mesh.num_cells, optional=True)
+        self._check_tracer_state(u_primitive, "u_primitive", self.mesh.num_cells, optional=True)
+        _lib.check(_lib.load().rdyhip_tracer_output_mean_accumulate(self._h, int(vars), float(dt), _ptr(u_solution) if u_solution is not None else None,
+                                                                   _ptr(u_primitive) if u_primitive is not None else None, _stream()))
+
+    def tracers_output_mean(self, var: int):
+        """rdyhip_tracer_output_mean_get: (mean [owned, 3 + NT], accumulated time) of one variable; nothing is reset"""
+        out = torch.empty((self.mesh.num_owned_cells, 3 + self.num_tracers), dtype=torch.float64, device="cuda")
+        t = C.c_double()
+        _lib.check(_lib.load().rdyhip_tracer_output_mean_get(self._h, int(var), _ptr(out), C.byref(t), _stream()))
+        return out, t.value
+
+    def tracers_reset_output_means(self, vars: int):
+        """rdyhip_tracer_output_mean_reset: accumulators and times of `vars` back to zero, on the current stream"""
+        _lib.check(_lib.load().rdyhip_tracer_output_mean_reset(self._h, int(vars), _stream()))
+
+    def tracers_output_mean_time(self, var: int) -> float:
+        t = C.c_double()
+        _lib.check(_lib.load().rdyhip_tracer_output_mean_time(self._h, int(var), C.byref(t)))
+        return t.value
+
+    def tracers_enable_observation_series(self, owned_cell_ids, capacity: int):
+        """rdyhip_tracer_series_enable: a device log of `capacity` records of the 3 + NT-wide state in the cells `owned_cell_ids`
+        (owned-cell indices; a site may repeat)"""
+        ids = np.ascontiguousarray(owned_cell_ids, dtype=np.int32).ravel()
+        arg = ids if ids.size else np.zeros(1, dtype=np.int32)
+        _lib.check(_lib.load().rdyhip_tracer_series_enable(self._h, int(ids.size), arg.ctypes.data_as(_lib.c_int32_p), int(capacity)))
+
+    def tracers_series_record(self, time: float, u_local: torch.Tensor):
+        """rdyhip_tracer_series_record: one record of the state `u_local` appended to the log, one launch on the current stream"""
+        self._check_tracer_state(u_local, "u_local", self.mesh.num_cells)
+        _lib.check(_lib.load().rdyhip_tracer_series_record(self._h, float(time), _ptr(u_local), _stream()))
+
+    def tracers_series_info(self) -> dict:
+        """rdyhip_tracer_series_info: rows of a record, records in the log, capacity"""
+        e, n, cap = C.c_int32(), C.c_int32(), C.c_int32()
+        _lib.check(_lib.load().rdyhip_tracer_series_info(self._h, C.byref(e), C.byref(n), C.byref(cap)))
+        return {"entries": e.value, "count": n.value, "capacity": cap.value}
+
+    def tracers_series_read(self, first: int = 0, count: Optional[int] = None):
+        """rdyhip_tracer_series_read: (times [count], values [count, entries, 3 + NT]) of records [first, first + count) as numpy
+        arrays (count=None: all from `first`); synchronises the current stream"""
+        info = self.tracers_series_info()
+        if count is None:
+            count = max(info["count"] - int(first), 0)
+        times = np.zeros(max(int(count), 0))
+        values = np.zeros((max(int(count), 0), info["entries"], 3 + self.num_tracers))
+        tp = times.ctypes.data_as(_lib.c_double_p) if times.size else None
+        vp = values.ctypes.data_as(_lib.c_double_p) if values.size else None
+        _lib.check(_lib.load().rdyhip_tracer_series_read(self._h, int(first), int(count), tp, vp, _stream()))
+        return times, values
+
+    def tracers_series_clear(self):
+        """rdyhip_tracer_series_clear: the log holds no records"""
+        _lib.check(_lib.load().rdyhip_tracer_series_clear(self._h))
 
     # -- ensembles (src/ensemble.c): B members on this mesh, state [B, num_cells, 3], one launch per evaluation ---------------------
     num_members = 0

@@ -338,12 +338,24 @@ class TracerEulerStepper:
     With a `halo` (HaloExchange, transport="c") every step is HaloExchange.tracers_step_overlapped -- the ghost update of the
     3 + NT-wide state and the step in one call -- so only the owned rows of the arrays need to be current between steps."""
 
-    def __init__(self, op, halo=None):
+    def __init__(self, op, halo=None, means: int = 0, series: Optional[TimeSeries] = None):
+        """`means` (OUTPUT_* bits; 0, the default: none of the operator's tracer output-mean calls is made): the stepper enables
+        the [owned, 3 + NT] accumulators and, after every step, accumulates with solution = the step's output and primitive
+        variables = the step's input state, weighted with the step's dt.  `series` (a TimeSeries; None, the default: no series
+        call is made): its observation sites are enabled, and after every step whose count is a multiple of
+        observation_interval a record of the step's output is appended at the stepper's time.  There is no boundary-flux series
+        for tracers, and -- unlike EulerStepper -- no monitor call before the first step."""
         self.op = op
         self.halo = halo
         self.step = 0
         self.time = 0.0
         self._own = [None, None]  # the stepper's arrays: the partner of the caller's array, and the partner of that one
+        self.means = int(means)
+        if self.means:
+            op.tracers_enable_output_means(self.means)
+        self.series = series
+        if series is not None and series.observation_interval:
+            op.tracers_enable_observation_series(series.observation_sites, series.capacity)
 
     def _partner(self, u: torch.Tensor) -> torch.Tensor:
         """as EnsembleEulerStepper._partner: never `u`, never another array of the caller's"""
@@ -364,7 +376,25 @@ class TracerEulerStepper:
                 self.halo.tracers_step_overlapped(self.op, dt, cur, nxt)
             else:
                 self.op.tracers_euler_step(dt, cur, nxt)
+            if self.means:
+                self.op.tracers_accumulate_output_means(self.means, dt, nxt, cur)   # solution: the step's output; primitive: its input
             cur, nxt = nxt, cur
             self.time += dt
             self.step += 1
+            s = self.series
+            if s is not None and s.observation_interval and self.step % s.observation_interval == 0:
+                self.op.tracers_series_record(self.time, cur)
         return cur
+
+    def series_read(self, clear: bool = False):
+        """the observation log, (times, values [records, sites, 3 + NT]); `clear`: the log then starts empty"""
+        out = self.op.tracers_series_read()
+        if clear:
+            self.op.tracers_series_clear()
+        return out
+
+    def output_mean(self, var: int):
+        """(mean [owned, 3 + NT], accumulated time) of one variable; its next window starts empty"""
+        mean, t = self.op.tracers_output_mean(var)
+        self.op.tracers_reset_output_means(var)
+        return mean, t
