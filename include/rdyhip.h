@@ -869,7 +869,34 @@ int rdyhip_error_sums_get(RDyHipOperator op, RDyHipErrorSums *out);
  *   operator, a null u_local on a rank with cells, u_local_out == u_local (or null), an unknown phase, unknown flag bits.
  * Every argument error (a null operator, tracers not enabled, a null array where one is needed, a tracer or boundary index out of
  * range, num_edges not the boundary's) is RDYHIP_ERR_USER and is reported before any device call.  A rank that owns nothing
- * launches nothing and succeeds. */
+ * launches nothing and succeeds.
+ *
+ * Under hydrostatic reconstruction (ApplyTracerInteriorFluxHR, ApplyTracerSourceHRSemiImplicit, tracer_petsc.c:807-986,
+ * 1067-1154; wired by CreatePetscFluxHROperator / CreatePetscSourceHROperator, src/operator_fluxes_petsc.c:59-95,
+ * src/operator_sources_petsc.c:30-45):
+ *   rdyhip_tracer_hr_enable   rdyhip_tracers_enable for an operator created with RDYHIP_WELL_BALANCING_HR: the same allocations,
+ *       the same bytes in device_bytes, the same range checks.  After it every call of this section and of "tracer output" works
+ *       unchanged and evaluates the HR form (tracer_hr_kernel, csrc/tracer_kernels.h); rdyhip_tracers_info keeps its two outputs.
+ *       rdyhip_tracers_enable itself keeps refusing such an operator (its message names this call).  Refused with
+ *       RDYHIP_ERR_USER before any device call, in this order: a null operator ("null operator"); tracers already enabled, by
+ *       either call; num_tracers outside 1..RDYHIP_MAX_TRACERS; an unknown `riemann`; second_order; an operator without HR (the
+ *       message points to rdyhip_tracers_enable); a source method other than semi-implicit ("Only semi_implicit is supported for
+ *       tracer HR", tracer_petsc.c:1191); a critical-outflow boundary.
+ *   rdyhip_tracer_hr_info     RDYHIP_WELL_BALANCING_HR after rdyhip_tracer_hr_enable, RDYHIP_WELL_BALANCING_NONE after
+ *       rdyhip_tracers_enable and while tracers are off.
+ * Arithmetic of an interior edge (boundary edges are those of the plain path: HR is a no-op there, operator_fluxes_petsc.c:79-93):
+ *   velocities of both cells in the ANUGA form hu h / (h^2 + h_anuga^2) under the HR operator's wet test h > tiny_h (869-875),
+ *   c_j = (h > tiny_h) ? h c_j / h : 0 (889-890); both depths reconstructed against max(zc_L, zc_R), h_rec = max(0, h + zc - z_max)
+ *   (863-867), velocities and concentrations unchanged, so the tracer flux sees h_rec c (892-893).  The edge contributes unless both
+ *   ORIGINAL depths are below tiny_h (922); inside that guard the 3 + NT flux components and the Courant candidate enter only where
+ *   hL_rec > tiny_h or hR_rec > tiny_h (939) -- with both at 0 the Roe solver's 0 / 0 is discarded by a branch, never multiplied
+ *   by zero --, and each side's pressure correction 0.5 g (h^2 - h_rec^2) (cn, sn) enters the two momentum components whenever the
+ *   outer guard holds (964-977), after the edge's flux.  The source has no bed slope; friction, erosion, deposition and the
+ *   primitive variables are those of the plain path.
+ * Two wet rules: interior edges use "h > tiny_h" with the regularised velocity; boundary edges, the source and the primitive
+ *   variables keep the plain path's "h < tiny_h => 0" (no regularisation on boundary edges and in the source).  They differ at
+ *   h == tiny_h exactly and where h_anuga != 0.  The stated differences above (owned-side Courant rule, boundary fluxes stored where
+ *   the left cell is owned) hold as they are. */
 #define RDYHIP_MAX_TRACERS 7                 /* MAX_NUM_TRACERS: 5 sediment classes + salinity + temperature (CMakeLists.txt:12-22) */
 #define RDYHIP_TRACER_RIEMANN_ROE 0          /* ComputeTracerRoeFlux */
 #define RDYHIP_TRACER_RIEMANN_UPWIND_ROE 1   /* ComputeUpwindTracerRoeFlux (RIEMANN_UPWIND_ROE) */
@@ -889,6 +916,9 @@ int rdyhip_tracer_phase_euler_step(RDyHipOperator op, int32_t phase, int32_t fla
 /* ghost update of the [num_cells][3 + NT] state + the evaluation, as rdyhip_rhs_overlapped / rdyhip_euler_step_overlapped */
 int rdyhip_halo_tracers_rhs(RDyHipOperator op, RDyHipHalo halo, double dt, double *u_local, double *f_global, void *stream);
 int rdyhip_halo_tracers_euler_step(RDyHipOperator op, RDyHipHalo halo, double dt, double *u_local, double *u_local_out, double *f_global, void *stream);
+/* tracers under hydrostatic reconstruction: the enable for an operator created with RDYHIP_WELL_BALANCING_HR, and which form runs */
+int rdyhip_tracer_hr_enable(RDyHipOperator op, int32_t num_tracers, int32_t riemann);
+int rdyhip_tracer_hr_info(RDyHipOperator op, int32_t *well_balancing);   /* RDYHIP_WELL_BALANCING_NONE or _HR; NONE also when tracers are off */
 
 /* ---- tracer output: read-out, error sums, output means and observation series of the [num_cells][3 + NT] state ----------------
  * What the three sections "time-averaged output fields", "time series on the device" and "state read-out" above do for rows of

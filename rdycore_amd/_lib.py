@@ -148,6 +148,8 @@ SYMBOLS = {
     "rdyhip_tracer_phase_euler_step": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rdyhip_halo_tracers_rhs": (C.c_int, [_H, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rdyhip_halo_tracers_euler_step": (C.c_int, [_H, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rdyhip_tracer_hr_enable": (C.c_int, [_H, C.c_int32, C.c_int32]),
+    "rdyhip_tracer_hr_info": (C.c_int, [_H, c_int32_p]),
     "rdyhip_tracer_state_planes": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rdyhip_tracer_state_read_begin": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "rdyhip_tracer_state_read_ready": (C.c_int, [_H, c_int32_p]),

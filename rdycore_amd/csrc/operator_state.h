@@ -191,6 +191,7 @@ struct TracerState {
   int32_t        n = 0, riemann = 0;   // 0 tracers: not enabled
   DevBuf<double> bvalues, bflux, src, pv;
   bool           pv_wanted = false;
+  bool           hr = false;           // enabled by rdyhip_tracer_hr_enable: the evaluations run tracer_hr_kernel
   size_t bytes() const { return bvalues.bytes() + bflux.bytes() + src.bytes() + pv.bytes(); }
 };
 

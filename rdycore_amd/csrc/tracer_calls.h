@@ -1,5 +1,6 @@
-// Shallow water with advected tracers behind the C ABI (rdyhip_tracers_*; kernel: tracer_kernels.h): the choice among the 28
-// instantiations, the launch, enable and the setters / getters of what only this path has.  Included by rdyhip_api.hip only.
+// Shallow water with advected tracers behind the C ABI (rdyhip_tracers_*, rdyhip_tracer_hr_*; kernels: tracer_kernels.h): the
+// choice among the 28 instantiations of either family (plain / hydrostatic reconstruction), the launch, the two enables and the
+// setters / getters of what only this path has.  Included by rdyhip_api.hip only.
 #pragma once
 namespace {
 
@@ -21,6 +22,24 @@ TracerKernelFn tracer_kernel_nt(int nt) {
 TracerKernelFn tracer_kernel_fn(int S, int nt, bool upwind) {
   return with_flag(S == 4, [&](auto quad) { return with_flag(upwind, [&](auto up) -> TracerKernelFn {
     return tracer_kernel_nt<quad ? 4 : 3, up>(nt);
+  }); });
+}
+// ... and of its twin under hydrostatic reconstruction (rdyhip_tracer_hr_enable): 28 more
+template <int S, bool UPWIND>
+TracerKernelFn tracer_hr_kernel_nt(int nt) {
+  switch (nt) {
+    case 1: return tracer_hr_kernel<S, 1, UPWIND>;
+    case 2: return tracer_hr_kernel<S, 2, UPWIND>;
+    case 3: return tracer_hr_kernel<S, 3, UPWIND>;
+    case 4: return tracer_hr_kernel<S, 4, UPWIND>;
+    case 5: return tracer_hr_kernel<S, 5, UPWIND>;
+    case 6: return tracer_hr_kernel<S, 6, UPWIND>;
+    default: return tracer_hr_kernel<S, 7, UPWIND>;
+  }
+}
+TracerKernelFn tracer_hr_kernel_fn(int S, int nt, bool upwind) {
+  return with_flag(S == 4, [&](auto quad) { return with_flag(upwind, [&](auto up) -> TracerKernelFn {
+    return tracer_hr_kernel_nt<quad ? 4 : 3, up>(nt);
   }); });
 }
 
@@ -64,7 +83,10 @@ int launch_tracers(RDyHipOperator op, double dt, const double *u, double *f, dou
   t.pv      = op->tracers.pv_wanted ? op->tracers.pv.p : nullptr;   // read here, when the launch is enqueued
   t.f       = f;
   t.u_out   = u_out;
-  TracerKernelFn kfn = tracer_kernel_fn(op->S, op->tracers.n, op->tracers.riemann == RDYHIP_TRACER_RIEMANN_UPWIND_ROE);
+  const bool upwind = op->tracers.riemann == RDYHIP_TRACER_RIEMANN_UPWIND_ROE;
+  // kernel_args_all_cells carries the slot tables (every operator has them) but not the bed elevations of an HR operator
+  if (op->tracers.hr) a.zc_local = op->d_zc_local.p;
+  TracerKernelFn kfn = op->tracers.hr ? tracer_hr_kernel_fn(op->S, op->tracers.n, upwind) : tracer_kernel_fn(op->S, op->tracers.n, upwind);
   hipLaunchKernelGGL(HIP_KERNEL_NAME(kfn), dim3(op->grid), dim3(BLOCK), 0, st, a, t, dt, u);
   HIP_TRY(hipGetLastError());
   return 0;
@@ -184,18 +206,27 @@ extern "C" int rdyhip_halo_tracers_euler_step(RDyHipOperator op, RDyHipHalo halo
   return tracers_overlapped(op, halo, true, dt, u_local, f_global, u_local_out, (hipStream_t)stream);
 }
 
-extern "C" int rdyhip_tracers_enable(RDyHipOperator op, int32_t num_tracers, int32_t riemann) {
+// rdyhip_tracers_enable (hr == false) / rdyhip_tracer_hr_enable (hr == true): the checks in the order the header lists them, then
+// the allocations -- the same for both
+static int tracers_enable(RDyHipOperator op, int32_t num_tracers, int32_t riemann, bool hr) {
   if (!op) return fail(RDYHIP_ERR_USER, "null operator");
-  if (op->tracers.n != 0) return fail(RDYHIP_ERR_USER, "tracers are already enabled (%d)", op->tracers.n);
+  if (op->tracers.n != 0)
+    return fail(RDYHIP_ERR_USER, "tracers are already enabled (%d%s)", op->tracers.n, op->tracers.hr ? ", hydrostatic reconstruction" : "");
   if (num_tracers < 1 || num_tracers > RDYHIP_MAX_TRACERS)
     return fail(RDYHIP_ERR_USER, "num_tracers (%d) must be in 1..%d", num_tracers, RDYHIP_MAX_TRACERS);
   if (riemann != RDYHIP_TRACER_RIEMANN_ROE && riemann != RDYHIP_TRACER_RIEMANN_UPWIND_ROE)
     return fail(RDYHIP_ERR_USER, "unknown tracer Riemann solver %d", riemann);
   if (op->muscl || op->config.second_order) return fail(RDYHIP_ERR_USER, "tracers are first order only (the operator was created with second_order)");
-  if (op->hr || op->config.well_balancing != RDYHIP_WELL_BALANCING_NONE)
-    return fail(RDYHIP_ERR_USER, "tracers with well balancing are not supported (well_balancing = %d)", op->config.well_balancing);
+  const bool op_hr = op->hr || op->config.well_balancing != RDYHIP_WELL_BALANCING_NONE;
+  if (!hr && op_hr)
+    return fail(RDYHIP_ERR_USER, "rdyhip_tracers_enable is for operators without well balancing (well_balancing = %d): use rdyhip_tracer_hr_enable",
+                op->config.well_balancing);
+  if (hr && !(op->hr && op->config.well_balancing == RDYHIP_WELL_BALANCING_HR))
+    return fail(RDYHIP_ERR_USER, "rdyhip_tracer_hr_enable needs an operator created with RDYHIP_WELL_BALANCING_HR (well_balancing = %d): use rdyhip_tracers_enable",
+                op->config.well_balancing);
   if (op->config.source_method != RDYHIP_SOURCE_SEMI_IMPLICIT)
-    return fail(RDYHIP_ERR_USER, "tracers have the semi-implicit source only (source_method = %d)", op->config.source_method);
+    return fail(RDYHIP_ERR_USER, hr ? "Only semi_implicit is supported for tracer HR (source_method = %d)"   // tracer_petsc.c:1191
+                                    : "tracers have the semi-implicit source only (source_method = %d)", op->config.source_method);
   for (size_t k = 0; k < op->h_btype.size(); ++k)
     if (op->h_btype[k] == RDYHIP_CONDITION_CRITICAL_OUTFLOW)
       return fail(RDYHIP_ERR_USER, "CONDITION_CRITICAL_OUTFLOW not supported for tracers");   // tracer_petsc.c:472-474
@@ -209,7 +240,18 @@ extern "C" int rdyhip_tracers_enable(RDyHipOperator op, int32_t num_tracers, int
   if (rc) return rc;
   t.n         = num_tracers;
   t.riemann   = riemann;
+  t.hr        = hr;
   op->tracers = std::move(t);
+  return 0;
+}
+
+extern "C" int rdyhip_tracers_enable(RDyHipOperator op, int32_t num_tracers, int32_t riemann) { return tracers_enable(op, num_tracers, riemann, false); }
+
+extern "C" int rdyhip_tracer_hr_enable(RDyHipOperator op, int32_t num_tracers, int32_t riemann) { return tracers_enable(op, num_tracers, riemann, true); }
+
+extern "C" int rdyhip_tracer_hr_info(RDyHipOperator op, int32_t *well_balancing) {
+  if (!op) return fail(RDYHIP_ERR_USER, "null operator");
+  if (well_balancing) *well_balancing = op->tracers.n != 0 && op->tracers.hr ? RDYHIP_WELL_BALANCING_HR : RDYHIP_WELL_BALANCING_NONE;
   return 0;
 }
 

@@ -228,4 +228,187 @@ __global__ __launch_bounds__(BLOCK) void tracer_rhs_kernel(const KernelArgs a, c
   block_courant_reduce<BLOCK>(a, best, RDY_COLD(a, pos), (best_slot < 0 ? 0 : best_slot) * a.stride + o);
 }
 
+// ---- tracers under hydrostatic reconstruction (rdyhip_tracer_hr_enable) ---------------------------------------------------------
+// ApplyTracerInteriorFluxHR + ApplyTracerSourceHRSemiImplicit (tracer_petsc.c:807-986, 1067-1154) in the shape of
+// tracer_rhs_kernel: the same thread per owned cell, slot order, phases, TracerArgs, stores and Courant bucket.  What differs
+// is the interior slot and the bed slope:
+//   velocities     of both cells in the ANUGA form hu h / (h^2 + h_anuga^2) under the HR operator's wet test h > tiny_h
+//                  (869-875): riemann_side(..., h_anuga_sq) and hr_velocity_rule;  c_j = (h > tiny_h) ? h c_j / h : 0 (889-890)
+//   depths         both reconstructed against max(zc_L, zc_R) (hr_reconstruct, swe_kernels.h); velocities and concentrations
+//                  pass through, so the tracer components of tracer_roe_flux see h_rec c (892-893)
+//   guards         the edge counts unless both ORIGINAL depths are below tiny_h (922); inside that, the N flux components and
+//                  the Courant candidate only where a reconstructed depth exceeds tiny_h (939) -- with both at 0 the Roe
+//                  solver returns 0 / 0, which a branch discards --; the own side's pressure correction
+//                  0.5 g (h^2 - h_rec^2) (cn, sn) whenever the outer guard holds (964-977), after the edge's flux
+//   boundary slots as in tracer_rhs_kernel (operator_fluxes_petsc.c:79-93: HR is a no-op there) with that kernel's rule for
+//                  the own cell (h < tiny_h => 0, no regularisation); the source keeps that rule too and has no bed slope
+// The own cell therefore carries two rule sets; they differ only at h == tiny_h exactly and where h_anuga != 0.
+template <int S, int NT, bool UPWIND>
+__global__ __launch_bounds__(BLOCK) void tracer_hr_kernel(const KernelArgs a, const TracerArgs t, const double dt, const double *__restrict__ u) {
+  constexpr int N = 3 + NT;
+  const int     i = xcd_block(a.xcd_chunks) * BLOCK + threadIdx.x;
+
+  double best      = 0.0;
+  int    best_slot = -1;
+  int    o         = 0;
+
+  bool           active = i < a.n_work;
+  int32_t        id[S];
+  const int32_t *nbr = RDY_COLD(a, nbr);
+  if (active) {
+    o              = i;
+    bool has_ghost = false;
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      id[s] = nbr[s * a.stride + o];
+      has_ghost |= (id[s] >= 0) && (id[s] & NBR_GHOST);
+    }
+    if (a.phase == RDYHIP_PHASE_INTERIOR && has_ghost) active = false;
+    if (a.phase == RDYHIP_PHASE_HALO && !has_ghost) active = false;
+  }
+  if (active) {
+    const int32_t *btype = RDY_COLD(a, btype);
+    const double  *cn_ = RDY_COLD(a, cn), *sn_ = RDY_COLD(a, sn);
+
+    const int64_t c = a.o2l ? a.o2l[o] : o;
+    double        own[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) own[k] = u[N * c + k];
+    const double z_self = a.zc_local[c];
+    // boundary edges and the source: the plain tracer path's own cell
+    const RiemannSide self = riemann_side(own[0], own[1], own[2], a.tiny_h, 0.0);
+    double            self_c[NT];
+    tracer_concentrations<NT>(own[0], own + 3, a.tiny_h, self_c);
+    // interior edges: the HR operator's (its concentrations are self_c under the strict test, selected where they are used)
+    RiemannSide self_hr = riemann_side(own[0], own[1], own[2], a.tiny_h, a.h_anuga_sq);
+    hr_velocity_rule(self_hr, a.tiny_h);
+    const bool self_wet_hr = own[0] > a.tiny_h;
+
+    double acc[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) acc[k] = 0.0;
+
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      const int32_t nid = id[s];
+      if (nid == NBR_EMPTY) continue;
+      const double cn   = cn_[s * a.stride + o];
+      const double sn   = sn_[s * a.stride + o];
+      const double coef = a.coef[s * a.stride + o];
+      const double cfac = fabs(coef);
+      double       fl[N], amax;
+      if (nid >= 0) {
+        const int64_t n = nid & NBR_MASK;
+        double        oth[N];
+#pragma unroll
+        for (int k = 0; k < N; ++k) oth[k] = u[N * n + k];
+        const double z_other = a.zc_local[n];
+        RiemannSide  other   = riemann_side(oth[0], oth[1], oth[2], a.tiny_h, a.h_anuga_sq);
+        hr_velocity_rule(other, a.tiny_h);
+        const bool   other_wet = oth[0] > a.tiny_h;
+        const double inv       = rdy_rcp(oth[0]);
+        const bool   self_left = coef < 0.0;
+        RiemannSide  L, R, Lr, Rr;
+        orient_sides(self_hr, other, self_left, L, R);
+        double cl[NT], cr[NT];
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+          const double cs = self_wet_hr ? self_c[j] : 0.0;
+          const double co = other_wet ? oth[3 + j] * inv : 0.0;
+          cl[j]           = self_left ? cs : co;
+          cr[j]           = self_left ? co : cs;
+        }
+        hr_reconstruct(L, R, self_left ? z_self : z_other, self_left ? z_other : z_self, Lr, Rr);
+        amax = tracer_roe_flux<NT, UPWIND>(Lr, Rr, cl, cr, sn, cn, fl);
+        if (!(R.h < a.tiny_h && L.h < a.tiny_h)) {
+          if (Lr.h > a.tiny_h || Rr.h > a.tiny_h) {
+#pragma unroll
+            for (int k = 0; k < N; ++k) acc[k] += fl[k] * coef;
+            const double cnum = amax * cfac * dt;
+            if (cnum > best) {
+              best      = cnum;
+              best_slot = s;
+            }
+          }
+          const double h_rec = self_left ? Lr.h : Rr.h;
+          const double corr  = 0.5 * GRAVITY * (own[0] * own[0] - h_rec * h_rec);
+          acc[1] += corr * cn * coef;
+          acc[2] += corr * sn * coef;
+        }
+      } else {
+        // ApplyTracerBoundaryFlux, exactly as in tracer_rhs_kernel
+        const int64_t k = -1 - nid;
+        RiemannSide   R;
+        double        cr[NT];
+        if (btype[k] == RDYHIP_CONDITION_DIRICHLET) {
+          double bv[N];
+#pragma unroll
+          for (int q = 0; q < N; ++q) bv[q] = t.bvalues[N * k + q];
+          R = riemann_side(bv[0], bv[1], bv[2], a.tiny_h, 0.0);
+          tracer_concentrations<NT>(bv[0], bv + 3, a.tiny_h, cr);
+        } else {
+          const double dum1 = sn * sn - cn * cn;
+          const double dum2 = 2.0 * sn * cn;
+          R.h               = self.h;
+          R.u               = self.u * dum1 - self.v * dum2;
+          R.v               = -self.u * dum2 - self.v * dum1;
+          R.sqh             = self.sqh;
+          R.c               = self.c;
+#pragma unroll
+          for (int j = 0; j < NT; ++j) cr[j] = self_c[j];
+        }
+        amax = tracer_roe_flux<NT, UPWIND>(self, R, self_c, cr, sn, cn, fl);
+#pragma unroll
+        for (int q = 0; q < N; ++q) t.bflux[N * k + q] = fl[q];
+        if (!(self.h < a.tiny_h && R.h < a.tiny_h)) {
+#pragma unroll
+          for (int k2 = 0; k2 < N; ++k2) acc[k2] += fl[k2] * coef;
+          const double cnum = amax * cfac * dt;
+          if (cnum > best) {
+            best      = cnum;
+            best_slot = s;
+          }
+        }
+      }
+    }
+
+    // sources (ApplyTracerSourceHRSemiImplicit): no bed slope; friction, erosion and deposition as in tracer_rhs_kernel
+    const double h = own[0];
+    const double n = a.mannings[o];
+    double       bedx, bedy, tbx, tby;
+    cell_source<RDYHIP_SOURCE_SEMI_IMPLICIT>(a, dt, h, own[1], own[2], acc[1], acc[2], 0.0, 0.0, n, bedx, bedy, tbx, tby);
+    double F[N];
+    F[0] = acc[0] + a.extsrc[3 * (int64_t)o + 0];
+    F[1] = acc[1] + (-bedx - tbx + a.extsrc[3 * (int64_t)o + 1]);
+    F[2] = acc[2] + (-bedy - tby + a.extsrc[3 * (int64_t)o + 2]);
+    const bool   cell_wet = h >= a.tiny_h;
+    const double Cd       = GRAVITY * (n * n) * rcbrt(h);
+    const double tau_b    = 0.5 * TRACER_RHO_WATER * Cd * (self.u * self.u + self.v * self.v);
+    const double ei       = TRACER_KP * (tau_b - TRACER_TAU_EROSION) / TRACER_TAU_EROSION;
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+      const double di = TRACER_SETTLING * self_c[j] * (1.0 - tau_b / TRACER_TAU_DEPOSITION);
+      F[3 + j]        = cell_wet ? acc[3 + j] + ((ei - di) + t.src[NT * (int64_t)o + j]) : acc[3 + j];
+    }
+
+    if (t.f) {
+#pragma unroll
+      for (int k = 0; k < N; ++k) RDY_ST(&t.f[N * (int64_t)o + k], F[k]);
+    }
+    if (t.pv) {
+      const RiemannSide p = riemann_side(h, own[1], own[2], a.tiny_h, a.h_anuga_sq);
+      RDY_ST(&t.pv[N * (int64_t)o + 0], h);
+      RDY_ST(&t.pv[N * (int64_t)o + 1], p.u);
+      RDY_ST(&t.pv[N * (int64_t)o + 2], p.v);
+#pragma unroll
+      for (int j = 0; j < NT; ++j) RDY_ST(&t.pv[N * (int64_t)o + 3 + j], self_c[j]);
+    }
+    if (t.u_out) {
+#pragma unroll
+      for (int k = 0; k < N; ++k) RDY_ST(&t.u_out[N * c + k], fma(dt, F[k], own[k]));
+    }
+  }
+  block_courant_reduce<BLOCK>(a, best, RDY_COLD(a, pos), (best_slot < 0 ? 0 : best_slot) * a.stride + o);
+}
+
 }  // namespace rdyhip

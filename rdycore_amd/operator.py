@@ -421,11 +421,24 @@ class Operator:
     # -- shallow water with advected tracers (src/tracer/tracer_petsc.c): state [num_cells, 3 + NT] = (h, hu, hv, h c_0 ...) --------
     num_tracers = 0
 
-    def enable_tracers(self, n: int, riemann: int = TRACER_RIEMANN_ROE):
+    def enable_tracers(self, n: int, riemann: int = TRACER_RIEMANN_ROE, well_balancing: int = WELL_BALANCING_NONE):
         """rdyhip_tracers_enable: the tracer path with `n` tracers (1..7) and the Roe (0) or upwind Roe (1) tracer flux; allocates
-        its boundary values / fluxes [K, 3 + n] and tracer sources [owned, n], all zero"""
-        _lib.check(_lib.load().rdyhip_tracers_enable(self._h, int(n), int(riemann)))
+        its boundary values / fluxes [K, 3 + n] and tracer sources [owned, n], all zero.  well_balancing=WELL_BALANCING_HR:
+        rdyhip_tracer_hr_enable, the same on an operator created with hydrostatic reconstruction (every tracer call then
+        evaluates the HR form); the default refuses such an operator."""
+        if well_balancing == WELL_BALANCING_HR:
+            _lib.check(_lib.load().rdyhip_tracer_hr_enable(self._h, int(n), int(riemann)))
+        elif well_balancing == WELL_BALANCING_NONE:
+            _lib.check(_lib.load().rdyhip_tracers_enable(self._h, int(n), int(riemann)))
+        else:
+            raise ValueError(f"well_balancing is WELL_BALANCING_NONE or WELL_BALANCING_HR, not {well_balancing}")
         self.num_tracers = int(n)
+
+    def tracers_well_balancing(self) -> int:
+        """rdyhip_tracer_hr_info: WELL_BALANCING_HR after enable_tracers(..., well_balancing=WELL_BALANCING_HR), else WELL_BALANCING_NONE"""
+        wb = C.c_int32()
+        _lib.check(_lib.load().rdyhip_tracer_hr_info(self._h, C.byref(wb)))
+        return wb.value
 
     def tracers_info(self) -> Tuple[int, int]:
         """rdyhip_tracers_info: (number of tracers -- 0: not enabled --, tracer Riemann solver)"""
