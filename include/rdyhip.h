@@ -91,6 +91,10 @@ typedef struct {
  *   that takes the step through rdyhip_euler_step (F never stored) or lets F sit (RK stages summed later) leaves it clear.
  *   Honoured by the first-order and HR tiled kernels; the second-order kernels keep the hint. */
 #define RDYHIP_CONFIG_CACHED_F_STORES 1
+/* STREAMED_NORMALS: keeps the normal table off (see rdyhip_normal_table_info): every first-order / HR launch streams one
+ *   double per edge record and rebuilds the normal from it, whatever the mesh.  The results are the same to the last bit
+ *   either way; the bit is there for tests and for A/B timings of the two kernel families. */
+#define RDYHIP_CONFIG_STREAMED_NORMALS 2
 
 /* The RDyMesh arrays the SWE operators read (include/private/rdymeshimpl.h:26-202).
  * All host pointers, borrowed for the duration of rdyhip_create() only. */
@@ -379,6 +383,15 @@ int rdyhip_source_is_water_only(RDyHipOperator op, int32_t *out);
 #define RDYHIP_UNIFORM_MANNINGS 2
 #define RDYHIP_UNIFORM_FLAT_BED 4
 int rdyhip_uniform_fields(RDyHipOperator op, int32_t *mask);
+/* The normal table.  The unit normals of a mesh cut from a raster take a handful of values (axis-parallel sides and the
+ * diagonals, in both orientations: six or eight), and the mesh is static for the life of an operator.  rdyhip_create counts
+ * the distinct normals of the tile edge records -- bit patterns, -0.0 is not +0.0 -- and, where there are at most 64, keeps
+ * them in a table of the operator: the first-order / HR tiled kernels then take each edge's normal from on-chip memory
+ * (kernel family swe_rhs_ntab_kernel) instead of streaming 8 B per record (swe_rhs_tiled_kernel).  Same results, bit for bit.
+ *   *entries = the size of the table, *active = 1 if the operator's launches use it; (0, 0) for a mesh with more normals
+ * or without edge records, under RDYHIP_CONFIG_STREAMED_NORMALS, for second_order and under RDYHIP_KERNEL=cell.  Either
+ * pointer may be NULL.  Uses no device memory: rdyhip_device_bytes is what it was. */
+int rdyhip_normal_table_info(RDyHipOperator op, int32_t *entries, int32_t *active);
 /* A device array of external sources ends the water-only mode of the source: this call does not block, so the host cannot
  * look at the momentum entries (keeping the plane on this path is a follow-up).  A host array keeps or restarts it. */
 int rdyhip_refresh_field(RDyHipOperator op, RDyHipField field, const double *values, int64_t num_values, int32_t values_on_device, void *stream);

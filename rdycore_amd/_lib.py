@@ -96,6 +96,7 @@ SYMBOLS = {
     "rdyhip_field_ptr_const": (C.c_int, [_H, C.c_int, C.POINTER(C.c_void_p), c_int64_p]),
     "rdyhip_source_is_water_only": (C.c_int, [_H, c_int32_p]),
     "rdyhip_uniform_fields": (C.c_int, [_H, c_int32_p]),
+    "rdyhip_normal_table_info": (C.c_int, [_H, c_int32_p, c_int32_p]),
     "rdyhip_field_release": (C.c_int, [_H, C.c_int]),
     "rdyhip_primitive_variables_stored": (C.c_int, [_H, c_int32_p]),
     "rdyhip_enable_flux_divergence": (C.c_int, [_H, C.c_int32]),

@@ -142,10 +142,10 @@ def kernel_resources(lib: str) -> dict:
     return {names[m]: v for m, v in out.items()}
 
 
-# swe_rhs_tiled_kernel<S, SRC, OVW, HR, EULER, FNT> / swe_rhs_muscl_fused_kernel<S, SRC, OVW, LIM, EULER>: the fifth template
+# swe_rhs_tiled_kernel / swe_rhs_ntab_kernel<S, SRC, OVW, HR, EULER, FNT> / swe_rhs_muscl_fused_kernel<S, SRC, OVW, LIM, EULER>: the fifth template
 # argument says whether a kernel is the RHS or its Euler-step instantiation (rdyhip_euler_step).  A profiled bench run launches
 # both about as often; the profile tools tell them apart by this, never by launch counts.
-_EULER_RX = re.compile(r"swe_rhs_(tiled_kernel<\d, \d, (?:true|false), (?:true|false), true, (?:true|false)>|muscl_fused_kernel<\d, \d, (?:true|false), \d, true>)")
+_EULER_RX = re.compile(r"swe_rhs_((?:tiled|ntab)_kernel<\d, \d, (?:true|false), (?:true|false), true, (?:true|false)>|muscl_fused_kernel<\d, \d, (?:true|false), \d, true>)")
 
 
 def is_euler_step_kernel(name: str) -> bool:

@@ -383,7 +383,7 @@ __global__ __launch_bounds__(TILE) void swe_rhs_muscl_fused_kernel(const KernelA
   // take over the gradients' storage once every edge has been evaluated: ~37-40 KB per workgroup, so FOUR workgroups of the
   // triangle kernel share a CU's 160 KB.
   using LAY = typename std::conditional<S == 3, MusclSoATri, MusclSoAQuad>::type;
-  extern __shared__ double lds[];
+  extern __shared__ __attribute__((aligned(16))) double lds[];  // as in swe_tiled_body.h: one declaration of the array per translation unit
   double   *sg  = lds;                                             // 6 planes of LAY::ng
   double   *sq  = lds + 6 * LAY::ng;                               // h, hu, hv, centroid x, centroid y: 5 planes of LAY::nq
   double   *ef  = sg;                                              // the edge fluxes: 4 planes of LAY::ne

@@ -303,6 +303,10 @@ struct RDyHipOperator_s : LayoutCounts {
   DevBuf<double>   d_zc_local;
   DevBuf<TileDesc> d_tiles;
   DevBuf<uint32_t> d_e_lr;
+  // The normal table (normal_table.h): > 0 entries: d_e_lr carries their indices, ColdArgs::nt_* the entries, and every
+  // first-order / HR launch runs the table family (swe_rhs_ntab_kernel) with ntab_lds_bytes of LDS.  Fixed at create.
+  int32_t          ntab_entries = 0;
+  size_t           ntab_lds_bytes = 0;
   DevBuf<int32_t>  d_hcells, d_tile_bk, d_tile_boff, d_halo_tiles, d_e_pos, d_x_lr;
   DevBuf<uint32_t> d_x_flags;
   DevBuf<double>   d_x_cs, d_x_cfac, d_x_mid;

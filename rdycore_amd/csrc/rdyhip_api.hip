@@ -38,6 +38,7 @@
 #include "error.h"
 #include "tile_format.h"
 #include "host_layout.h"
+#include "normal_table.h"
 #include "swe_device.h"
 #include "swe_kernels.h"
 #include "forcing_kernels.h"
@@ -69,11 +70,16 @@ auto with_flag(bool b, F f) {
 }
 
 // The instantiation of the tiled kernel for (slots per cell, source method, f = rhs (else f += rhs), HR, the forward-Euler update
-// fused into the stores (rdyhip_euler_step; always f = rhs), F -- Euler step: u_out -- stored with the non-temporal hint)
-TiledKernelFn tiled_kernel_fn(int S, int src, bool ovw, bool hr, bool euler, bool fnt) {
+// fused into the stores (rdyhip_euler_step; always f = rhs), F -- Euler step: u_out -- stored with the non-temporal hint,
+// normals from the operator's table (swe_rhs_ntab_kernel) instead of one streamed double per record)
+TiledKernelFn tiled_kernel_fn(int S, int src, bool ovw, bool hr, bool euler, bool fnt, bool ntab) {
   return with_flag(S == 4, [&](auto quad) { return with_flag(src != 0, [&](auto xq) { return with_flag(hr, [&](auto hr_) {
     return with_flag(fnt, [&](auto nt) -> TiledKernelFn {
       constexpr int s = quad ? 4 : 3, x = xq ? 1 : 0;
+      if (ntab) {
+        if (euler) return swe_rhs_ntab_kernel<s, x, true, hr_, true, nt>;
+        return ovw ? swe_rhs_ntab_kernel<s, x, true, hr_, false, nt> : swe_rhs_ntab_kernel<s, x, false, hr_, false, nt>;
+      }
       if (euler) return swe_rhs_tiled_kernel<s, x, true, hr_, true, nt>;
       return ovw ? swe_rhs_tiled_kernel<s, x, true, hr_, false, nt> : swe_rhs_tiled_kernel<s, x, false, hr_, false, nt>;
     });
@@ -258,7 +264,8 @@ int launch_rhs(RDyHipOperator op, int32_t phase, int32_t overwrite, int reset_di
     } else {
       // plain (cached) stores: of u_out for states that fit the Infinity Cache, of F under RDYHIP_CONFIG_CACHED_F_STORES
       const bool     cached = euler_fused ? op->uout_cached : (op->config.flags & RDYHIP_CONFIG_CACHED_F_STORES) != 0;
-      TiledKernelFn  kfn    = tiled_kernel_fn(op->S, xq ? 1 : 0, overwrite != 0, op->hr, euler_fused, !cached);
+      const bool     ntab   = op->ntab_entries > 0;  // fixed at create: d_e_lr carries the indices, the cold block the entries
+      TiledKernelFn  kfn    = tiled_kernel_fn(op->S, xq ? 1 : 0, overwrite != 0, op->hr, euler_fused, !cached, ntab);
       // the flag is read here, when the launch is enqueued: launches and source writers on one stream stay consistent
       if (op->src_water_only) {
         a.extsrc  = op->d_src_water.p;
@@ -277,7 +284,7 @@ int launch_rhs(RDyHipOperator op, int32_t phase, int32_t overwrite, int reset_di
       a.tile_walk = dyn_ok && dyn_want ? TILE_WALK_DYNAMIC
                     : a.phase == RDYHIP_PHASE_INTERIOR                                                ? TILE_WALK_STATIC_SKIP
                                                                                                        : TILE_WALK_STATIC;
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(kfn), dim3(grid), dim3(TILE), op->lds_bytes, st, a, dt, u, f);
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(kfn), dim3(grid), dim3(TILE), ntab ? op->ntab_lds_bytes : op->lds_bytes, st, a, dt, u, f);
     }
   } else {
     grid = cell_launch_work(op, phase, a);
@@ -352,6 +359,14 @@ int rdyhip_create(const RDyHipConfig *config, const RDyHipMesh *mesh, int32_t nu
     if ((op->hr || op->muscl) && !op->use_tiled)
       return fail(RDYHIP_ERR_USER, "hydrostatic reconstruction and second_order are implemented by the tiled kernels only (unset RDYHIP_KERNEL=cell)");
   }
+  // The normal table, for the operators that launch the first-order / HR tiled kernels: on the copy of the records that is
+  // uploaded below (the layout pass and rdyhip_probe_layout know nothing of it).  Where the mesh has too many normals the words
+  // stay as they are and the operator streams.
+  NormalTable ntab;
+  if (op->use_tiled && !op->muscl && !(config->flags & RDYHIP_CONFIG_STREAMED_NORMALS))
+    ntab = build_normal_table(L.e_lr.data(), L.e_cs.data(), std::min(L.e_lr.size(), L.e_cs.size()));
+  op->ntab_entries   = ntab.active ? (int32_t)ntab.cs.size() : 0;
+  op->ntab_lds_bytes = tiled_ntab_lds_bytes(S, op->hr);
   if (hipGetDevice(&op->device) != hipSuccess) return fail(RDYHIP_ERR_LIB, "hipGetDevice failed: no usable HIP device");
 
   const int tiles_n = (op->n_owned + BLOCK - 1) / BLOCK;
@@ -366,8 +381,9 @@ int rdyhip_create(const RDyHipConfig *config, const RDyHipMesh *mesh, int32_t nu
     if (hipGetDeviceProperties(&prop, op->device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
     if (const char *e2 = getenv("RDYHIP_BLOCKS_PER_CU")) per_cu_forced = atoi(e2);
     int q = 0;
-    const void *kfn = (const void *)tiled_kernel_fn(S, xq, true, op->hr, false, true);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, kfn, TILE, op->lds_bytes) == hipSuccess && q > 0) per_cu = q;
+    const bool  nt  = op->ntab_entries > 0;
+    const void *kfn = (const void *)tiled_kernel_fn(S, xq, true, op->hr, false, true, nt);
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, kfn, TILE, nt ? op->ntab_lds_bytes : op->lds_bytes) == hipSuccess && q > 0) per_cu = q;
     // the family's own setting (tiled_blocks_per_cu): a kernel compiled for three waves per SIMD may well fit four
     per_cu = std::min(per_cu, tiled_blocks_per_cu(S, xq, op->hr));
     if (per_cu_forced > 0) per_cu = per_cu_forced;
@@ -454,6 +470,11 @@ int rdyhip_create(const RDyHipConfig *config, const RDyHipMesh *mesh, int32_t nu
     c.x_cfac = op->d_x_cfac.p; c.x_mid = op->d_x_mid.p;
     c.blk_max = op->d_blk_max.p; c.blk_pos = op->d_blk_pos.p;
     c.tile_draw = op->d_tile_draw.p;
+    c.nt_count  = op->ntab_entries;
+    for (int32_t i = 0; i < op->ntab_entries; ++i) {
+      c.nt_cs[i]    = ntab.cs[i];
+      c.nt_flags[i] = ntab.flags[i];
+    }
     rc = op->d_cold.upload(std::vector<ColdArgs>(1, c));
   }
   if (rc) return rc;
@@ -624,6 +645,13 @@ static_assert(UNIFORM_SOURCE == RDYHIP_UNIFORM_SOURCE && UNIFORM_MANNINGS == RDY
 int rdyhip_uniform_fields(RDyHipOperator op, int32_t *mask) {
   if (!op || !mask) return fail(RDYHIP_ERR_USER, "null argument");
   *mask = op->uniform.mask(op->src_water_only);
+  return 0;
+}
+
+int rdyhip_normal_table_info(RDyHipOperator op, int32_t *entries, int32_t *active) {
+  if (!op) return fail(RDYHIP_ERR_USER, "null operator");
+  if (entries) *entries = op->ntab_entries;
+  if (active) *active = op->ntab_entries > 0 ? 1 : 0;
   return 0;
 }
 

@@ -43,6 +43,13 @@ constexpr uint32_t EDGE_OTHER_NEG    = 1u << 24;  // the reconstructed component
 // second order: the edge belongs to another rank (edges.is_owned = false): ApplyInteriorFlux2R evaluates its Courant number
 // there (swe_petsc.c:172-190); here its flux still feeds the owned cell, its wave speed is kept out of the diagnostic
 constexpr uint32_t EDGE_NOT_OWNED    = 1u << 25;
+// Normal table (normal_table.h): where the edges of a mesh have at most NORMAL_TABLE_MAX distinct (stored component, CS_IS_CN,
+// OTHER_NEG) triples -- a raster-derived mesh has six or eight -- bits 26-31 of a record's word hold the index of its triple
+// in a table of the operator (ColdArgs::nt_*), and the first-order / HR table kernels (swe_rhs_ntab_kernel) do not read e_cs.
+// Every other reader masks the fields it uses, so the words serve both families.
+constexpr int      NORMAL_TABLE_MAX   = 64;
+constexpr int      EDGE_NT_SHIFT      = 26;
+constexpr uint32_t EDGE_NT_FLAGS      = EDGE_CS_IS_CN | EDGE_OTHER_NEG;  // what a table entry keeps of a word
 // slot references of a triangle mesh (S == 3): 3 x 10 bits in one uint32, 0x3FF = unused
 constexpr uint32_t REF3_EMPTY = 0x3FF;
 
@@ -66,6 +73,12 @@ constexpr int TILED_NS_TRI = TILE + TILE_MAX_HALO_TRI, TILED_NS_QUAD = TILE + TI
 constexpr size_t tiled_lds_bytes(int S, bool hr) {
   return sizeof(double) * ((hr ? 6 : 5) * (size_t)(S == 3 ? TILED_NS_TRI : TILED_NS_QUAD) + 2 * (size_t)TILE + (hr ? 6 : 4) * (size_t)TILED_NE);
 }
+// ... of the table kernels: the same planes, then the (cn, sn) pairs of the normal table, 16 B each (the planes end on a
+// multiple of 16 B in all four families)
+constexpr size_t tiled_ntab_lds_bytes(int S, bool hr) { return tiled_lds_bytes(S, hr) + 2 * sizeof(double) * (size_t)NORMAL_TABLE_MAX; }
+static_assert(tiled_lds_bytes(3, false) % 16 == 0 && tiled_lds_bytes(3, true) % 16 == 0 && tiled_lds_bytes(4, false) % 16 == 0 &&
+                  tiled_lds_bytes(4, true) % 16 == 0 && tiled_ntab_lds_bytes(4, true) <= 64 * 1024,
+              "the planes ahead of the normal table are a multiple of 16 B (the array itself is declared aligned(16)), and the table fits a workgroup's 64 KB");
 
 // second order (muscl_kernels.h): MusclArgs::bn_idx entries that are no LDS slot
 constexpr uint16_t BN_NONE = 0xFFFF, BN_GLOBAL = 0xFFFE;

@@ -50,6 +50,7 @@ class RDyFlowConfig:
     second_order: bool = False        # numerics.second_order: MUSCL reconstruction (src/swe/swe_petsc.c:98-213)
     limiter: int = LIMITER_MINMOD     # numerics.limiter
     cached_f_stores: bool = False     # RDYHIP_CONFIG_CACHED_F_STORES: F is read back by a separate update kernel (TSEULER's VecAXPY)
+    streamed_normals: bool = False    # RDYHIP_CONFIG_STREAMED_NORMALS: no normal table, whatever the mesh (tests, A/B timings)
 
 
 @dataclasses.dataclass
@@ -120,7 +121,8 @@ def _abi_arguments(config: "RDyFlowConfig", mesh: RDyMesh, condition_types: Opti
         barr[i].condition_type = int(condition_types[i])
     cfg = _lib.RDyHipConfig(config.tiny_h, config.h_anuga_regular, config.xq2018_threshold,
                             int(config.source_method), int(config.riemann), int(config.well_balancing),
-                            1 if config.second_order else 0, int(config.limiter), 1 if getattr(config, "cached_f_stores", False) else 0)
+                            1 if config.second_order else 0, int(config.limiter),
+                            (1 if getattr(config, "cached_f_stores", False) else 0) | (2 if getattr(config, "streamed_normals", False) else 0))
     return cfg, m, nb, barr, list(condition_types), keep
 
 
@@ -874,6 +876,13 @@ class Operator:
         out = C.c_int32()
         _lib.check(_lib.load().rdyhip_uniform_fields(self._h, C.byref(out)))
         return int(out.value)
+
+    def normal_table_info(self) -> Tuple[int, bool]:
+        """rdyhip_normal_table_info: (entries, active) -- active: the operator's first-order / HR launches take the edge normals
+        from its table of `entries` distinct ones (kernel family swe_rhs_ntab_kernel); (0, False): they stream them."""
+        n, act = C.c_int32(), C.c_int32()
+        _lib.check(_lib.load().rdyhip_normal_table_info(self._h, C.byref(n), C.byref(act)))
+        return int(n.value), bool(act.value)
 
     @property
     def mannings_n(self) -> torch.Tensor:
