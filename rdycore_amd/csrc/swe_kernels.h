@@ -744,6 +744,22 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(tiled_bloc
 // ---------------------------------------------------------------------------
 // cell-centric kernel: one thread = one owned cell, all of its edges
 // ---------------------------------------------------------------------------
+// The neighbour ids of owned cell o, and whether the cell is of the launch's phase: ghost adjacency is the NBR_GHOST bit of an
+// id (a.phase is uniform per launch).  For the cell-centric kernels here and in tracer_kernels.h.  (`active` as a variable,
+// not early returns: with those swe_rhs_kernel compiles to other machine code.)
+template <int S>
+__device__ __forceinline__ bool cell_of_phase(const KernelArgs &a, const int32_t *nbr, int o, int32_t *id) {
+  bool active = true, has_ghost = false;
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    id[s] = nbr[s * a.stride + o];
+    has_ghost |= (id[s] >= 0) && (id[s] & NBR_GHOST);
+  }
+  if (a.phase == RDYHIP_PHASE_INTERIOR && has_ghost) active = false;
+  if (a.phase == RDYHIP_PHASE_HALO && !has_ghost) active = false;
+  return active;
+}
+
 template <int S, int SRC>
 __global__ __launch_bounds__(BLOCK) void swe_rhs_kernel(const KernelArgs a, const double dt, const double *__restrict__ u,
                                                         double *__restrict__ f) {
@@ -758,15 +774,8 @@ __global__ __launch_bounds__(BLOCK) void swe_rhs_kernel(const KernelArgs a, cons
   const int32_t *nbr = RDY_COLD(a, nbr), *btype = RDY_COLD(a, btype);  // one thread = one cell: read once per thread
   const double  *cn_ = RDY_COLD(a, cn), *sn_ = RDY_COLD(a, sn), *bvalues = RDY_COLD(a, bvalues);
   if (active) {
-    o              = a.list ? a.list[i] : i;
-    bool has_ghost = false;
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-      id[s] = nbr[s * a.stride + o];
-      has_ghost |= (id[s] >= 0) && (id[s] & NBR_GHOST);
-    }
-    if (a.phase == RDYHIP_PHASE_INTERIOR && has_ghost) active = false;
-    if (a.phase == RDYHIP_PHASE_HALO && !has_ghost) active = false;
+    o      = a.list ? a.list[i] : i;
+    active = cell_of_phase<S>(a, nbr, o, id);
   }
 
   if (active) {

@@ -6,40 +6,20 @@ namespace {
 
 using TracerKernelFn = void (*)(const KernelArgs, const TracerArgs, const double, const double *);
 
-// The instantiation of the tracer kernel for (slots per cell, number of tracers, upwind tracer flux): 2 x 7 x 2 = 28
-template <int S, bool UPWIND>
-TracerKernelFn tracer_kernel_nt(int nt) {
-  switch (nt) {
-    case 1: return tracer_rhs_kernel<S, 1, UPWIND>;
-    case 2: return tracer_rhs_kernel<S, 2, UPWIND>;
-    case 3: return tracer_rhs_kernel<S, 3, UPWIND>;
-    case 4: return tracer_rhs_kernel<S, 4, UPWIND>;
-    case 5: return tracer_rhs_kernel<S, 5, UPWIND>;
-    case 6: return tracer_rhs_kernel<S, 6, UPWIND>;
-    default: return tracer_rhs_kernel<S, 7, UPWIND>;
-  }
-}
-TracerKernelFn tracer_kernel_fn(int S, int nt, bool upwind) {
+// The instantiation of the tracer kernel for (family: hydrostatic reconstruction (rdyhip_tracer_hr_enable) or plain, slots per
+// cell, number of tracers, upwind tracer flux): 2 x (2 x 7 x 2) = 56
+TracerKernelFn tracer_kernel_fn(bool hr, int S, int nt, bool upwind) {
   return with_flag(S == 4, [&](auto quad) { return with_flag(upwind, [&](auto up) -> TracerKernelFn {
-    return tracer_kernel_nt<quad ? 4 : 3, up>(nt);
-  }); });
-}
-// ... and of its twin under hydrostatic reconstruction (rdyhip_tracer_hr_enable): 28 more
-template <int S, bool UPWIND>
-TracerKernelFn tracer_hr_kernel_nt(int nt) {
-  switch (nt) {
-    case 1: return tracer_hr_kernel<S, 1, UPWIND>;
-    case 2: return tracer_hr_kernel<S, 2, UPWIND>;
-    case 3: return tracer_hr_kernel<S, 3, UPWIND>;
-    case 4: return tracer_hr_kernel<S, 4, UPWIND>;
-    case 5: return tracer_hr_kernel<S, 5, UPWIND>;
-    case 6: return tracer_hr_kernel<S, 6, UPWIND>;
-    default: return tracer_hr_kernel<S, 7, UPWIND>;
-  }
-}
-TracerKernelFn tracer_hr_kernel_fn(int S, int nt, bool upwind) {
-  return with_flag(S == 4, [&](auto quad) { return with_flag(upwind, [&](auto up) -> TracerKernelFn {
-    return tracer_hr_kernel_nt<quad ? 4 : 3, up>(nt);
+    constexpr int s = quad ? 4 : 3;
+    switch (nt) {
+      case 1: return hr ? tracer_hr_kernel<s, 1, up> : tracer_rhs_kernel<s, 1, up>;
+      case 2: return hr ? tracer_hr_kernel<s, 2, up> : tracer_rhs_kernel<s, 2, up>;
+      case 3: return hr ? tracer_hr_kernel<s, 3, up> : tracer_rhs_kernel<s, 3, up>;
+      case 4: return hr ? tracer_hr_kernel<s, 4, up> : tracer_rhs_kernel<s, 4, up>;
+      case 5: return hr ? tracer_hr_kernel<s, 5, up> : tracer_rhs_kernel<s, 5, up>;
+      case 6: return hr ? tracer_hr_kernel<s, 6, up> : tracer_rhs_kernel<s, 6, up>;
+      default: return hr ? tracer_hr_kernel<s, 7, up> : tracer_rhs_kernel<s, 7, up>;
+    }
   }); });
 }
 
@@ -86,7 +66,7 @@ int launch_tracers(RDyHipOperator op, double dt, const double *u, double *f, dou
   const bool upwind = op->tracers.riemann == RDYHIP_TRACER_RIEMANN_UPWIND_ROE;
   // kernel_args_all_cells carries the slot tables (every operator has them) but not the bed elevations of an HR operator
   if (op->tracers.hr) a.zc_local = op->d_zc_local.p;
-  TracerKernelFn kfn = op->tracers.hr ? tracer_hr_kernel_fn(op->S, op->tracers.n, upwind) : tracer_kernel_fn(op->S, op->tracers.n, upwind);
+  TracerKernelFn kfn = tracer_kernel_fn(op->tracers.hr, op->S, op->tracers.n, upwind);
   hipLaunchKernelGGL(HIP_KERNEL_NAME(kfn), dim3(op->grid), dim3(BLOCK), 0, st, a, t, dt, u);
   HIP_TRY(hipGetLastError());
   return 0;

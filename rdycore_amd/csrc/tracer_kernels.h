@@ -73,16 +73,40 @@ __device__ __forceinline__ double tracer_roe_flux(const RiemannSide &L, const Ri
   return f.amax;
 }
 
-// One thread = one owned cell: the cell's own row is prepared once, its up to S slots are walked in slot order, the source
-// epilogue of ApplyTracerSourceSemiImplicit (tracer_petsc.c:617-737) and the stores follow; the Courant bucket goes through
-// block_courant_reduce with the `pos` table, so ties resolve as in swe_rhs_kernel.  f = F(u) only.
+// ---- the two kernel families: tracer_rhs_kernel (plain) and tracer_hr_kernel (hydrostatic reconstruction) ---------------------------
+// Both read: shared prologue (cell_of_phase, swe_kernels.h; tracer_own_cell below), the family's own interior slot, the shared
+// boundary slot (tracer_boundary_flux.h), the shared epilogue (tracer_epilogue.h), block_courant_reduce.  The prologue is two
+// functions: with them every result keeps its bits.  The boundary slot and the epilogue are files included in place: as
+// functions they change bits of F (see the two files).  "The edge counts" (acc += fl coef, the Courant candidate) stays where it
+// is, once in the plain kernel and twice in the HR one: as a function it changes the NaN payloads that bflux holds for edges dry
+// on both sides.  (What each form was measured to do: profiles/RESULTS_LOG.md section 32.)
+//
 // Phases (KernelArgs::phase, a run-time scalar: no further instantiations): every launch has one thread per owned cell, and a
-// thread whose cell is not of the launch's phase -- ghost adjacency is the NBR_GHOST bit of its neighbour ids, as in
-// swe_rhs_kernel -- loads and stores nothing and enters the reduction with best = 0.  A workgroup therefore has the same
-// Courant bucket in every phase, and a launch with reset_diag == 0 merges into it (block_courant_reduce).
+// thread whose cell is not of the launch's phase (cell_of_phase) loads nothing but its neighbour ids, stores nothing and enters
+// the reduction with best = 0.  A workgroup therefore has the same Courant bucket in every phase, and a launch with
+// reset_diag == 0 merges into it (block_courant_reduce).
+
+// The thread's own cell: its row of the state and, under the plain tracer path's rules (h < tiny_h => 0, no regularisation),
+// its Riemann side and concentrations -- what the boundary slots and the source of BOTH families use.  Returns the local id.
+// (Plain arrays, no struct: carried in one, two instantiations of tracer_hr_kernel take 6 VGPRs more and lose a wave per SIMD.)
+template <int NT>
+__device__ __forceinline__ int64_t tracer_own_cell(const KernelArgs &a, const double *__restrict__ u, int o, double *own, RiemannSide &self, double *self_c) {
+  const int64_t c = a.o2l ? a.o2l[o] : o;
+#pragma unroll
+  for (int k = 0; k < 3 + NT; ++k) own[k] = u[(3 + NT) * c + k];
+  self = riemann_side(own[0], own[1], own[2], a.tiny_h, 0.0);
+  tracer_concentrations<NT>(own[0], own + 3, a.tiny_h, self_c);
+  return c;
+}
+
+// ---- the plain family (rdyhip_tracers_enable) ------------------------------------------------------------------------------------
+// One thread = one owned cell: the prologue prepares the cell's own row once, its up to S slots are walked in slot order -- the
+// interior slot below is this family's own --, the source epilogue of ApplyTracerSourceSemiImplicit and the stores follow; the
+// Courant bucket goes through block_courant_reduce with the `pos` table, so ties resolve as in swe_rhs_kernel.  f = F(u) only.
 template <int S, int NT, bool UPWIND>
 __global__ __launch_bounds__(BLOCK) void tracer_rhs_kernel(const KernelArgs a, const TracerArgs t, const double dt, const double *__restrict__ u) {
-  constexpr int N = 3 + NT;
+  constexpr bool HR = false;
+  constexpr int  N  = 3 + NT;
   const int     i = xcd_block(a.xcd_chunks) * BLOCK + threadIdx.x;
 
   double best      = 0.0;
@@ -93,28 +117,15 @@ __global__ __launch_bounds__(BLOCK) void tracer_rhs_kernel(const KernelArgs a, c
   int32_t        id[S];
   const int32_t *nbr = RDY_COLD(a, nbr);
   if (active) {
-    o              = i;
-    bool has_ghost = false;
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-      id[s] = nbr[s * a.stride + o];
-      has_ghost |= (id[s] >= 0) && (id[s] & NBR_GHOST);
-    }
-    // a cell of the other phase: nothing but its neighbour ids is loaded, nothing is stored (a.phase is uniform per launch)
-    if (a.phase == RDYHIP_PHASE_INTERIOR && has_ghost) active = false;
-    if (a.phase == RDYHIP_PHASE_HALO && !has_ghost) active = false;
+    o      = i;
+    active = cell_of_phase<S>(a, nbr, o, id);
   }
   if (active) {
     const int32_t *btype = RDY_COLD(a, btype);
     const double  *cn_ = RDY_COLD(a, cn), *sn_ = RDY_COLD(a, sn);
-
-    const int64_t c = a.o2l ? a.o2l[o] : o;
-    double        own[N];
-#pragma unroll
-    for (int k = 0; k < N; ++k) own[k] = u[N * c + k];
-    const RiemannSide self = riemann_side(own[0], own[1], own[2], a.tiny_h, 0.0);
-    double            self_c[NT];
-    tracer_concentrations<NT>(own[0], own + 3, a.tiny_h, self_c);
+    double         own[N], self_c[NT];
+    RiemannSide    self;
+    const int64_t  c = tracer_own_cell<NT>(a, u, o, own, self, self_c);
 
     double acc[N];
 #pragma unroll
@@ -150,30 +161,8 @@ __global__ __launch_bounds__(BLOCK) void tracer_rhs_kernel(const KernelArgs a, c
         amax = tracer_roe_flux<NT, UPWIND>(L, R, cl, cr, sn, cn, fl);
         wet  = !(R.h < a.tiny_h && L.h < a.tiny_h);
       } else {
-        // ApplyTracerBoundaryFlux (tracer_petsc.c:405-525): the cell is the left one.  Critical outflow is refused at
-        // rdyhip_tracers_enable (472-474), so a type that is not Dirichlet is reflecting.
-        const int64_t k = -1 - nid;
-        RiemannSide   R;
-        double        cr[NT];
-        if (btype[k] == RDYHIP_CONDITION_DIRICHLET) {
-          double bv[N];
-#pragma unroll
-          for (int q = 0; q < N; ++q) bv[q] = t.bvalues[N * k + q];
-          R = riemann_side(bv[0], bv[1], bv[2], a.tiny_h, 0.0);
-          tracer_concentrations<NT>(bv[0], bv + 3, a.tiny_h, cr);
-        } else {  // ApplyTracerReflectingBC (362-395): h and c_i copied, the velocity mirrored
-          const double dum1 = sn * sn - cn * cn;
-          const double dum2 = 2.0 * sn * cn;
-          R.h               = self.h;
-          R.u               = self.u * dum1 - self.v * dum2;
-          R.v               = -self.u * dum2 - self.v * dum1;
-          R.sqh             = self.sqh;
-          R.c               = self.c;
-#pragma unroll
-          for (int j = 0; j < NT; ++j) cr[j] = self_c[j];
-        }
-        amax = tracer_roe_flux<NT, UPWIND>(self, R, self_c, cr, sn, cn, fl);
-        wet  = !(self.h < a.tiny_h && R.h < a.tiny_h);
+#include "tracer_boundary_flux.h"
+        wet = !(self.h < a.tiny_h && R.h < a.tiny_h);
 #pragma unroll
         for (int q = 0; q < N; ++q) t.bflux[N * k + q] = fl[q];
       }
@@ -187,51 +176,16 @@ __global__ __launch_bounds__(BLOCK) void tracer_rhs_kernel(const KernelArgs a, c
         }
       }
     }
-
-    // sources: bed slope, semi-implicit friction on the pre-source momentum sums, erosion - deposition for wet cells
-    const double h = own[0];
-    const double n = a.mannings[o];
-    double       bedx, bedy, tbx, tby;
-    cell_source<RDYHIP_SOURCE_SEMI_IMPLICIT>(a, dt, h, own[1], own[2], acc[1], acc[2], a.dzdx[o], a.dzdy[o], n, bedx, bedy, tbx, tby);
-    double F[N];
-    F[0] = acc[0] + a.extsrc[3 * (int64_t)o + 0];
-    F[1] = acc[1] + (-bedx - tbx + a.extsrc[3 * (int64_t)o + 1]);
-    F[2] = acc[2] + (-bedy - tby + a.extsrc[3 * (int64_t)o + 2]);
-    const bool   cell_wet = h >= a.tiny_h;
-    const double Cd       = GRAVITY * (n * n) * rcbrt(h);
-    const double tau_b    = 0.5 * TRACER_RHO_WATER * Cd * (self.u * self.u + self.v * self.v);  // h >= tiny_h: self.u = hu / h
-    const double ei       = TRACER_KP * (tau_b - TRACER_TAU_EROSION) / TRACER_TAU_EROSION;
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      const double di = TRACER_SETTLING * self_c[j] * (1.0 - tau_b / TRACER_TAU_DEPOSITION);
-      F[3 + j]        = cell_wet ? acc[3 + j] + ((ei - di) + t.src[NT * (int64_t)o + j]) : acc[3 + j];
-    }
-
-    if (t.f) {
-#pragma unroll
-      for (int k = 0; k < N; ++k) RDY_ST(&t.f[N * (int64_t)o + k], F[k]);
-    }
-    // primitive variables (tracer_petsc.c:715-724): the regularised velocities, c_i = h c_i / h, all zero below tiny_h
-    if (t.pv) {
-      const RiemannSide p = riemann_side(h, own[1], own[2], a.tiny_h, a.h_anuga_sq);
-      RDY_ST(&t.pv[N * (int64_t)o + 0], h);
-      RDY_ST(&t.pv[N * (int64_t)o + 1], p.u);
-      RDY_ST(&t.pv[N * (int64_t)o + 2], p.v);
-#pragma unroll
-      for (int j = 0; j < NT; ++j) RDY_ST(&t.pv[N * (int64_t)o + 3 + j], self_c[j]);
-    }
-    if (t.u_out) {
-#pragma unroll
-      for (int k = 0; k < N; ++k) RDY_ST(&t.u_out[N * c + k], fma(dt, F[k], own[k]));
-    }
+#include "tracer_epilogue.h"
   }
   block_courant_reduce<BLOCK>(a, best, RDY_COLD(a, pos), (best_slot < 0 ? 0 : best_slot) * a.stride + o);
 }
 
 // ---- tracers under hydrostatic reconstruction (rdyhip_tracer_hr_enable) ---------------------------------------------------------
-// ApplyTracerInteriorFluxHR + ApplyTracerSourceHRSemiImplicit (tracer_petsc.c:807-986, 1067-1154) in the shape of
-// tracer_rhs_kernel: the same thread per owned cell, slot order, phases, TracerArgs, stores and Courant bucket.  What differs
-// is the interior slot and the bed slope:
+// ApplyTracerInteriorFluxHR + ApplyTracerSourceHRSemiImplicit (tracer_petsc.c:807-986, 1067-1154): the prologue, the boundary
+// slot and the epilogue are tracer_rhs_kernel's own (the same functions, the same included files).  What this kernel states
+// itself is three lines for the own cell (z_self, self_hr, self_wet_hr) and the interior slot; the epilogue drops the bed slope
+// under `HR`:
 //   velocities     of both cells in the ANUGA form hu h / (h^2 + h_anuga^2) under the HR operator's wet test h > tiny_h
 //                  (869-875): riemann_side(..., h_anuga_sq) and hr_velocity_rule;  c_j = (h > tiny_h) ? h c_j / h : 0 (889-890)
 //   depths         both reconstructed against max(zc_L, zc_R) (hr_reconstruct, swe_kernels.h); velocities and concentrations
@@ -240,12 +194,13 @@ __global__ __launch_bounds__(BLOCK) void tracer_rhs_kernel(const KernelArgs a, c
 //                  the Courant candidate only where a reconstructed depth exceeds tiny_h (939) -- with both at 0 the Roe
 //                  solver returns 0 / 0, which a branch discards --; the own side's pressure correction
 //                  0.5 g (h^2 - h_rec^2) (cn, sn) whenever the outer guard holds (964-977), after the edge's flux
-//   boundary slots as in tracer_rhs_kernel (operator_fluxes_petsc.c:79-93: HR is a no-op there) with that kernel's rule for
+//   boundary slots tracer_boundary_flux.h (operator_fluxes_petsc.c:79-93: HR is a no-op there), with the plain path's rule for
 //                  the own cell (h < tiny_h => 0, no regularisation); the source keeps that rule too and has no bed slope
 // The own cell therefore carries two rule sets; they differ only at h == tiny_h exactly and where h_anuga != 0.
 template <int S, int NT, bool UPWIND>
 __global__ __launch_bounds__(BLOCK) void tracer_hr_kernel(const KernelArgs a, const TracerArgs t, const double dt, const double *__restrict__ u) {
-  constexpr int N = 3 + NT;
+  constexpr bool HR = true;
+  constexpr int  N  = 3 + NT;
   const int     i = xcd_block(a.xcd_chunks) * BLOCK + threadIdx.x;
 
   double best      = 0.0;
@@ -256,31 +211,18 @@ __global__ __launch_bounds__(BLOCK) void tracer_hr_kernel(const KernelArgs a, co
   int32_t        id[S];
   const int32_t *nbr = RDY_COLD(a, nbr);
   if (active) {
-    o              = i;
-    bool has_ghost = false;
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-      id[s] = nbr[s * a.stride + o];
-      has_ghost |= (id[s] >= 0) && (id[s] & NBR_GHOST);
-    }
-    if (a.phase == RDYHIP_PHASE_INTERIOR && has_ghost) active = false;
-    if (a.phase == RDYHIP_PHASE_HALO && !has_ghost) active = false;
+    o      = i;
+    active = cell_of_phase<S>(a, nbr, o, id);
   }
   if (active) {
     const int32_t *btype = RDY_COLD(a, btype);
     const double  *cn_ = RDY_COLD(a, cn), *sn_ = RDY_COLD(a, sn);
-
-    const int64_t c = a.o2l ? a.o2l[o] : o;
-    double        own[N];
-#pragma unroll
-    for (int k = 0; k < N; ++k) own[k] = u[N * c + k];
-    const double z_self = a.zc_local[c];
-    // boundary edges and the source: the plain tracer path's own cell
-    const RiemannSide self = riemann_side(own[0], own[1], own[2], a.tiny_h, 0.0);
-    double            self_c[NT];
-    tracer_concentrations<NT>(own[0], own + 3, a.tiny_h, self_c);
-    // interior edges: the HR operator's (its concentrations are self_c under the strict test, selected where they are used)
-    RiemannSide self_hr = riemann_side(own[0], own[1], own[2], a.tiny_h, a.h_anuga_sq);
+    double         own[N], self_c[NT];
+    RiemannSide    self;
+    const int64_t  c = tracer_own_cell<NT>(a, u, o, own, self, self_c);
+    // interior edges: the HR operator's own cell (its concentrations are self_c under the strict test, selected where they are used)
+    const double z_self  = a.zc_local[c];
+    RiemannSide  self_hr = riemann_side(own[0], own[1], own[2], a.tiny_h, a.h_anuga_sq);
     hr_velocity_rule(self_hr, a.tiny_h);
     const bool self_wet_hr = own[0] > a.tiny_h;
 
@@ -336,28 +278,7 @@ __global__ __launch_bounds__(BLOCK) void tracer_hr_kernel(const KernelArgs a, co
           acc[2] += corr * sn * coef;
         }
       } else {
-        // ApplyTracerBoundaryFlux, exactly as in tracer_rhs_kernel
-        const int64_t k = -1 - nid;
-        RiemannSide   R;
-        double        cr[NT];
-        if (btype[k] == RDYHIP_CONDITION_DIRICHLET) {
-          double bv[N];
-#pragma unroll
-          for (int q = 0; q < N; ++q) bv[q] = t.bvalues[N * k + q];
-          R = riemann_side(bv[0], bv[1], bv[2], a.tiny_h, 0.0);
-          tracer_concentrations<NT>(bv[0], bv + 3, a.tiny_h, cr);
-        } else {
-          const double dum1 = sn * sn - cn * cn;
-          const double dum2 = 2.0 * sn * cn;
-          R.h               = self.h;
-          R.u               = self.u * dum1 - self.v * dum2;
-          R.v               = -self.u * dum2 - self.v * dum1;
-          R.sqh             = self.sqh;
-          R.c               = self.c;
-#pragma unroll
-          for (int j = 0; j < NT; ++j) cr[j] = self_c[j];
-        }
-        amax = tracer_roe_flux<NT, UPWIND>(self, R, self_c, cr, sn, cn, fl);
+#include "tracer_boundary_flux.h"
 #pragma unroll
         for (int q = 0; q < N; ++q) t.bflux[N * k + q] = fl[q];
         if (!(self.h < a.tiny_h && R.h < a.tiny_h)) {
@@ -371,42 +292,7 @@ __global__ __launch_bounds__(BLOCK) void tracer_hr_kernel(const KernelArgs a, co
         }
       }
     }
-
-    // sources (ApplyTracerSourceHRSemiImplicit): no bed slope; friction, erosion and deposition as in tracer_rhs_kernel
-    const double h = own[0];
-    const double n = a.mannings[o];
-    double       bedx, bedy, tbx, tby;
-    cell_source<RDYHIP_SOURCE_SEMI_IMPLICIT>(a, dt, h, own[1], own[2], acc[1], acc[2], 0.0, 0.0, n, bedx, bedy, tbx, tby);
-    double F[N];
-    F[0] = acc[0] + a.extsrc[3 * (int64_t)o + 0];
-    F[1] = acc[1] + (-bedx - tbx + a.extsrc[3 * (int64_t)o + 1]);
-    F[2] = acc[2] + (-bedy - tby + a.extsrc[3 * (int64_t)o + 2]);
-    const bool   cell_wet = h >= a.tiny_h;
-    const double Cd       = GRAVITY * (n * n) * rcbrt(h);
-    const double tau_b    = 0.5 * TRACER_RHO_WATER * Cd * (self.u * self.u + self.v * self.v);
-    const double ei       = TRACER_KP * (tau_b - TRACER_TAU_EROSION) / TRACER_TAU_EROSION;
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      const double di = TRACER_SETTLING * self_c[j] * (1.0 - tau_b / TRACER_TAU_DEPOSITION);
-      F[3 + j]        = cell_wet ? acc[3 + j] + ((ei - di) + t.src[NT * (int64_t)o + j]) : acc[3 + j];
-    }
-
-    if (t.f) {
-#pragma unroll
-      for (int k = 0; k < N; ++k) RDY_ST(&t.f[N * (int64_t)o + k], F[k]);
-    }
-    if (t.pv) {
-      const RiemannSide p = riemann_side(h, own[1], own[2], a.tiny_h, a.h_anuga_sq);
-      RDY_ST(&t.pv[N * (int64_t)o + 0], h);
-      RDY_ST(&t.pv[N * (int64_t)o + 1], p.u);
-      RDY_ST(&t.pv[N * (int64_t)o + 2], p.v);
-#pragma unroll
-      for (int j = 0; j < NT; ++j) RDY_ST(&t.pv[N * (int64_t)o + 3 + j], self_c[j]);
-    }
-    if (t.u_out) {
-#pragma unroll
-      for (int k = 0; k < N; ++k) RDY_ST(&t.u_out[N * c + k], fma(dt, F[k], own[k]));
-    }
+#include "tracer_epilogue.h"
   }
   block_courant_reduce<BLOCK>(a, best, RDY_COLD(a, pos), (best_slot < 0 ? 0 : best_slot) * a.stride + o);
 }

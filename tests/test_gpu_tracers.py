@@ -113,9 +113,8 @@ def _bits(a):
 COMBOS = [(1, TRACER_RIEMANN_ROE), (2, TRACER_RIEMANN_UPWIND_ROE), (7, TRACER_RIEMANN_ROE), (7, TRACER_RIEMANN_UPWIND_ROE)]
 
 
-@pytest.mark.parametrize("nt,riemann", COMBOS)
-@pytest.mark.parametrize("name", MESHES)
-def test_rhs_primitive_variables_boundary_fluxes_and_courant(name, nt, riemann):
+def _check_rhs(name, nt, riemann):
+    """one evaluation of a case: F, the primitive variables, the boundary fluxes and the Courant struct against the reference"""
     torch = _torch()
     case, ref, u, F = _case(name, nt, riemann)
     mesh = case.mesh
@@ -145,6 +144,21 @@ def test_rhs_primitive_variables_boundary_fluxes_and_courant(name, nt, riemann):
     assert ec[-1] - ec[-2] > 1e-9 * ec[-1], "the state has a near tie: choose another seed"
     assert (d.global_edge_id, d.global_cell_id) == (int(mesh.edge_global_ids[edge]), int(mesh.cell_global_ids[cell]))
     op.destroy()
+
+
+@pytest.mark.parametrize("nt,riemann", COMBOS)
+@pytest.mark.parametrize("name", MESHES)
+def test_rhs_primitive_variables_boundary_fluxes_and_courant(name, nt, riemann):
+    _check_rhs(name, nt, riemann)
+
+
+@pytest.mark.parametrize("riemann", [TRACER_RIEMANN_ROE, TRACER_RIEMANN_UPWIND_ROE])
+@pytest.mark.parametrize("nt", range(1, 8))
+@pytest.mark.parametrize("name", ["tri-30", "quad-44"])
+def test_every_instantiation_runs_on_the_device(name, nt, riemann):
+    """tracer_rhs_kernel<S, NT, UPWIND> for S = 3 (tri-30) and 4 (quad-44), NT = 1..7 and both tracer Riemann solvers: each of the 28
+    instantiations evaluated once, on the smallest meshes of this file, under the bars of the test above"""
+    _check_rhs(name, nt, riemann)
 
 
 @pytest.mark.parametrize("name,nt,riemann", [("tri-270", 2, TRACER_RIEMANN_UPWIND_ROE), ("part-o2l", 7, TRACER_RIEMANN_ROE), ("mixed", 1, TRACER_RIEMANN_ROE)])
