@@ -1033,7 +1033,7 @@ int rdyhip_tracer_series_clear(RDyHipOperator op);
  * rdyhip_ensemble_update_diagnostics: one merge launch for all members, one copy of B x 16 bytes, one stream synchronise;
  *   rdyhip_ensemble_get_diagnostics then returns each member's value and ids, translated as rdyhip_update_diagnostics does.  Of
  *   edges that tie, the first in the reference's loop order wins.
- * Supported: first order, well_balancing NONE, both source methods, all three boundary types, triangles, quads and mixed meshes,
+ * Supported: first order, well_balancing NONE (HR: rdyhip_ens_hr_enable, below), both source methods, all three boundary types, triangles, quads and mixed meshes,
  *   ranks with ghost cells.
  * Stated differences: there is no accumulated boundary-flux array.  Primitive variables and the flux divergence are not stored.
  *   The flux of a boundary edge is stored where its left cell is owned; rows of edges behind ghost cells are left as they are.  On
@@ -1043,8 +1043,26 @@ int rdyhip_tracer_series_clear(RDyHipOperator op);
  * Every argument error -- a null operator, num_members outside 1..RDYHIP_MAX_ENSEMBLE_MEMBERS, an operator created with
  *   second_order or hydrostatic reconstruction, a second enable, any other call before enable, a member, boundary or component
  *   index out of range, num_edges not the boundary's, a null array where one is needed -- is RDYHIP_ERR_USER and is reported
- *   before any device call.  A rank that owns nothing launches nothing and succeeds. */
+ *   before any device call.  A rank that owns nothing launches nothing and succeeds.
+ *
+ * Ensembles under hydrostatic reconstruction (members over real beds with wet / dry fronts):
+ *   rdyhip_ens_hr_enable   rdyhip_ensemble_enable for an operator created with RDYHIP_WELL_BALANCING_HR: the same allocations, the
+ *                          same copies of the operator's inputs into the members, the same member groups and checks; every
+ *                          rdyhip_ensemble_* call above then works unchanged -- and rdyhip_diagnostics_begin / _wait in the ensemble
+ *                          scope -- and evaluates ApplyInteriorFluxHR and the HR source (src/swe/swe_petsc.c:1000-1161, 1229-1263)
+ *                          of every member in one launch of ensemble_hr_kernel: interior edges reconstruct both depths against
+ *                          max(zc_L, zc_R) with the HR operator's wet test h > tiny_h and add each side's pressure correction,
+ *                          boundary edges are the plain path's (HR is a no-op there), the source has no bed slope.  Both source
+ *                          methods.  The bed elevations are the operator's own (shared by the members, like the mesh).
+ *                          Refused with RDYHIP_ERR_USER before any device call: an operator created without
+ *                          RDYHIP_WELL_BALANCING_HR, one created with second_order, a second enable (of either kind),
+ *                          num_members outside 1..RDYHIP_MAX_ENSEMBLE_MEMBERS.  rdyhip_ensemble_enable keeps refusing an HR
+ *                          operator.  The stated differences are those above.
+ *   rdyhip_ens_hr_info     RDYHIP_WELL_BALANCING_HR after rdyhip_ens_hr_enable, RDYHIP_WELL_BALANCING_NONE after
+ *                          rdyhip_ensemble_enable or before either. */
 #define RDYHIP_MAX_ENSEMBLE_MEMBERS 64
+int rdyhip_ens_hr_enable(RDyHipOperator op, int32_t num_members);
+int rdyhip_ens_hr_info(RDyHipOperator op, int32_t *well_balancing);   /* RDYHIP_WELL_BALANCING_NONE or _HR; NONE also when the ensemble is off */
 int rdyhip_ensemble_enable(RDyHipOperator op, int32_t num_members);
 int rdyhip_ensemble_info(RDyHipOperator op, int32_t *num_members);                 /* 0: not enabled */
 int rdyhip_ensemble_set_mannings(RDyHipOperator op, int32_t member, int32_t n, const int32_t *owned_cell_ids /* NULL: 0..n-1 */, const double *values /* host */);

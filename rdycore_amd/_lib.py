@@ -179,6 +179,8 @@ SYMBOLS = {
     "rdyhip_ensemble_get_boundary_fluxes": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, c_double_p]),
     "rdyhip_ensemble_update_diagnostics": (C.c_int, [_H, C.c_void_p]),
     "rdyhip_ensemble_get_diagnostics": (C.c_int, [_H, C.POINTER(RDyHipCourant)]),
+    "rdyhip_ens_hr_enable": (C.c_int, [_H, C.c_int32]),
+    "rdyhip_ens_hr_info": (C.c_int, [_H, c_int32_p]),
     "rdyhip_halo_create": (C.c_int, [_H, C.c_void_p, C.c_int32, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p, C.POINTER(C.c_void_p)]),
     "rdyhip_halo_destroy": (C.c_int, [C.POINTER(C.c_void_p)]),
     "rdyhip_halo_overlaps": (C.c_int32, [C.c_void_p]),

@@ -1,14 +1,17 @@
-// Ensembles behind the C ABI (rdyhip_ensemble_*; kernel: ensemble_kernels.h): B members on one mesh, one launch per
-// evaluation; enable, the members' setters / getters and their Courant diagnostics.  Included by rdyhip_api.hip only.
+// Ensembles behind the C ABI (rdyhip_ensemble_*, rdyhip_ens_hr_*; kernels: ensemble_kernels.h): B members on one mesh, one launch
+// per evaluation of either family (plain / hydrostatic reconstruction); the two enables, the members' setters / getters and
+// their Courant diagnostics.  Included by rdyhip_api.hip only.
 #pragma once
 namespace {
 
 using EnsembleKernelFn = void (*)(const KernelArgs, const EnsembleArgs, const double *);
 
-// The instantiation of the ensemble kernel for (slots per cell, source method, the fused Euler update): 2 x 2 x 2 = 8
-EnsembleKernelFn ensemble_kernel_fn(int S, int src, bool euler) {
+// The instantiation of the ensemble kernel for (family: hydrostatic reconstruction (rdyhip_ens_hr_enable) or plain, slots per
+// cell, source method, the fused Euler update): 2 x (2 x 2 x 2) = 16
+EnsembleKernelFn ensemble_kernel_fn(bool hr, int S, int src, bool euler) {
   return with_flag(S == 4, [&](auto quad) { return with_flag(src != 0, [&](auto xq) { return with_flag(euler, [&](auto eu) -> EnsembleKernelFn {
-    return ensemble_rhs_kernel<quad ? 4 : 3, xq ? 1 : 0, eu>;
+    constexpr int s = quad ? 4 : 3, sm = xq ? 1 : 0;
+    return hr ? ensemble_hr_kernel<s, sm, eu> : ensemble_rhs_kernel<s, sm, eu>;
   }); }); });
 }
 
@@ -30,7 +33,9 @@ int ensemble_check_member(RDyHipOperator op, int32_t member) {
 int launch_ensemble(RDyHipOperator op, const double *dts, const double *u, double *f, double *u_out, hipStream_t st) {
   for (auto &c : op->ensemble.courant) c = RDyHipCourant{0.0, -1, -1};
   if (op->n_owned == 0) return 0;   // a rank may own nothing: nothing to launch
-  const KernelArgs a = kernel_args_all_cells(op);   // Manning's n, the source and the Courant buckets are the members' own
+  KernelArgs a = kernel_args_all_cells(op);   // Manning's n, the source and the Courant buckets are the members' own
+  // kernel_args_all_cells carries the slot tables (every operator has them) but not the bed elevations of an HR operator
+  if (op->ensemble.hr) a.zc_local = op->d_zc_local.p;
   EnsembleArgs     t{};
   t.mannings  = op->ensemble.mannings.p;
   t.extsrc    = op->ensemble.extsrc.p;
@@ -46,7 +51,7 @@ int launch_ensemble(RDyHipOperator op, const double *dts, const double *u, doubl
   t.per_group = op->ensemble.per_group;
   t.n_buckets = ENSEMBLE_WAVES * op->grid;
   for (int m = 0; m < op->ensemble.members; ++m) t.dts[m] = dts[m];
-  EnsembleKernelFn kfn = ensemble_kernel_fn(op->S, op->config.source_method, u_out != nullptr);
+  EnsembleKernelFn kfn = ensemble_kernel_fn(op->ensemble.hr, op->S, op->config.source_method, u_out != nullptr);
   hipLaunchKernelGGL(HIP_KERNEL_NAME(kfn), dim3(op->grid, op->ensemble.groups), dim3(BLOCK), 0, st, a, t, u);
   HIP_TRY(hipGetLastError());
   return 0;
@@ -54,14 +59,21 @@ int launch_ensemble(RDyHipOperator op, const double *dts, const double *u, doubl
 
 }  // namespace
 
-extern "C" int rdyhip_ensemble_enable(RDyHipOperator op, int32_t num_members) {
+// rdyhip_ensemble_enable (hr == false) / rdyhip_ens_hr_enable (hr == true): the checks, every one before any device call, then
+// the allocations, the copies of the operator's inputs and the group rule -- the same for both
+static int ensemble_enable(RDyHipOperator op, int32_t num_members, bool hr) {
   if (!op) return fail(RDYHIP_ERR_USER, "null operator");
   if (op->ensemble.members != 0) return fail(RDYHIP_ERR_USER, "the ensemble is already enabled (%d members)", op->ensemble.members);
   if (num_members < 1 || num_members > RDYHIP_MAX_ENSEMBLE_MEMBERS)
     return fail(RDYHIP_ERR_USER, "num_members (%d) must be in 1..%d", num_members, RDYHIP_MAX_ENSEMBLE_MEMBERS);
   if (op->muscl || op->config.second_order) return fail(RDYHIP_ERR_USER, "ensembles are first order only (the operator was created with second_order)");
-  if (op->hr || op->config.well_balancing != RDYHIP_WELL_BALANCING_NONE)
-    return fail(RDYHIP_ERR_USER, "ensembles with well balancing are not supported (well_balancing = %d)", op->config.well_balancing);
+  const bool op_hr = op->hr || op->config.well_balancing != RDYHIP_WELL_BALANCING_NONE;
+  if (!hr && op_hr)
+    return fail(RDYHIP_ERR_USER, "ensembles with well balancing are not supported (well_balancing = %d) by rdyhip_ensemble_enable: use rdyhip_ens_hr_enable",
+                op->config.well_balancing);
+  if (hr && !(op->hr && op->config.well_balancing == RDYHIP_WELL_BALANCING_HR))
+    return fail(RDYHIP_ERR_USER, "rdyhip_ens_hr_enable needs an operator created with RDYHIP_WELL_BALANCING_HR (well_balancing = %d): use rdyhip_ensemble_enable",
+                op->config.well_balancing);
   const size_t B = (size_t)num_members, K = (size_t)op->K, no = (size_t)op->n_owned, W = (size_t)ENSEMBLE_WAVES * (size_t)op->grid;
   EnsembleState s;
   int rc = s.mannings.alloc(B * no);
@@ -85,7 +97,7 @@ extern "C" int rdyhip_ensemble_enable(RDyHipOperator op, int32_t num_members) {
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e != hipSuccess) return fail(RDYHIP_ERR_LIB, "rdyhip_ensemble_enable: a device copy failed: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return fail(RDYHIP_ERR_LIB, "%s: a device copy failed: %s", hr ? "rdyhip_ens_hr_enable" : "rdyhip_ensemble_enable", hipGetErrorString(e));
   // The member groups.  Few cells: one group per member, down to ENSEMBLE_MIN_WORKGROUPS workgroups in all, so that a small
   // mesh still puts several workgroups on every CU; many cells: every thread walks up to ENSEMBLE_MAX_PER_GROUP members with
   // its geometry.
@@ -94,8 +106,19 @@ extern "C" int rdyhip_ensemble_enable(RDyHipOperator op, int32_t num_members) {
   s.per_group  = std::min((num_members + g0 - 1) / g0, ENSEMBLE_MAX_PER_GROUP);
   s.groups     = (num_members + s.per_group - 1) / s.per_group;   // no group is empty
   s.members    = num_members;
+  s.hr         = hr;
   s.courant.assign(B, RDyHipCourant{0.0, -1, -1});
   op->ensemble = std::move(s);
+  return 0;
+}
+
+extern "C" int rdyhip_ensemble_enable(RDyHipOperator op, int32_t num_members) { return ensemble_enable(op, num_members, false); }
+
+extern "C" int rdyhip_ens_hr_enable(RDyHipOperator op, int32_t num_members) { return ensemble_enable(op, num_members, true); }
+
+extern "C" int rdyhip_ens_hr_info(RDyHipOperator op, int32_t *well_balancing) {
+  if (!op) return fail(RDYHIP_ERR_USER, "null operator");
+  if (well_balancing) *well_balancing = op->ensemble.members != 0 && op->ensemble.hr ? RDYHIP_WELL_BALANCING_HR : RDYHIP_WELL_BALANCING_NONE;
   return 0;
 }
 

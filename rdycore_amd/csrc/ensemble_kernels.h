@@ -20,6 +20,10 @@
 //
 // The inline functions of swe_device.h and swe_kernels.h are called as they are; KernelArgs / ColdArgs carry the operator's
 // shared tables, what only this path has travels in EnsembleArgs.
+//
+// Two kernel families share all of the above: ensemble_rhs_kernel (rdyhip_ensemble_enable) and, for operators created with
+// hydrostatic reconstruction, ensemble_hr_kernel (rdyhip_ens_hr_enable), whose geometry holds bed elevations where the bed
+// slopes were.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -145,6 +149,162 @@ __global__ __launch_bounds__(BLOCK) void ensemble_rhs_kernel(const KernelArgs a,
       const int64_t r = (int64_t)m * a.n_owned + o;
       double        bedx, bedy, tbx, tby;
       cell_source<SRC>(a, dt, h, hu, hv, acc1, acc2, dzdx, dzdy, RDY_LD(&t.mannings[r]), bedx, bedy, tbx, tby);
+      const double F0 = acc0 + RDY_LD(&t.extsrc[3 * r + 0]);
+      const double F1 = acc1 + (-bedx - tbx + RDY_LD(&t.extsrc[3 * r + 1]));
+      const double F2 = acc2 + (-bedy - tby + RDY_LD(&t.extsrc[3 * r + 2]));
+      if (!EULER || t.f) {
+        RDY_ST(&t.f[3 * r + 0], F0);
+        RDY_ST(&t.f[3 * r + 1], F1);
+        RDY_ST(&t.f[3 * r + 2], F2);
+      }
+      if (EULER) {
+        double *uo = t.u_out + (int64_t)m * t.u_stride;
+        RDY_ST(&uo[3 * c + 0], fma(dt, F0, h));
+        RDY_ST(&uo[3 * c + 1], fma(dt, F1, hu));
+        RDY_ST(&uo[3 * c + 2], fma(dt, F2, hv));
+      }
+    }
+    // the wave's bucket of member m: larger value, then the earlier edge (swe_petsc.c:291 keeps the first).  No barrier.
+    const double wmax = wave_max(best);
+    int          p    = INT32_MAX;
+    if (best > 0.0 && best == wmax) p = pos[(best_slot < 0 ? 0 : best_slot) * a.stride + o];
+    p = wave_min(p);
+    if (lane == 0) {
+      const int64_t b = (int64_t)m * t.n_buckets + bucket;
+      t.blk_max[b]    = wmax;
+      t.blk_pos[b]    = wmax > 0.0 ? p : -1;
+    }
+  }
+}
+
+// ---- ensembles under hydrostatic reconstruction (rdyhip_ens_hr_enable) -----------------------------------------------------------
+// ApplyInteriorFluxHR + the HR source (src/swe/swe_petsc.c:1000-1161, 1229-1263) for every member: ensemble_rhs_kernel's layout,
+// grid, member loop, buckets, EnsembleArgs and stores.  What HR needs beyond the plain kernel is GEOMETRY -- the cell's bed
+// elevation and its interior neighbours' (KernelArgs::zc_local, which the launch sets) -- loaded once per thread for all members
+// of its group, where the bed slopes (which the HR source does not read) were.  Per member, as in tracer_hr_kernel:
+//   own cell       two rule sets: riemann_side as it is for the boundary slots and the source (HR is a no-op at boundaries,
+//                  operator_fluxes_petsc.c:57-58), the same side after hr_velocity_rule (wet test h > tiny_h, 1061-1064) for the
+//                  interior slots; they differ only at h == tiny_h exactly
+//   interior slot  the neighbour under riemann_side + hr_velocity_rule, orient_sides, hr_reconstruct with the two elevations in
+//                  left / right order, roe_flux on the reconstructed sides.  The edge counts unless both ORIGINAL depths are
+//                  below tiny_h (1094); inside that, the flux and the Courant candidate only where a reconstructed depth
+//                  exceeds tiny_h (1112) -- a branch: with both at 0 the Roe solver returns 0 / 0 --; then, whenever the outer
+//                  guard holds, the own side's pressure correction 0.5 g (h^2 - h_rec^2) (cn, sn) coef (1136-1152)
+//   source         cell_source<SRC> with zero bed slopes, as the tiled HR family calls it
+template <int S, int SRC, bool EULER>
+__global__ __launch_bounds__(BLOCK) void ensemble_hr_kernel(const KernelArgs a, const EnsembleArgs t, const double *__restrict__ u) {
+  const int  i      = xcd_block(a.xcd_chunks) * BLOCK + threadIdx.x;
+  const bool active = i < a.n_work;
+  const int  o      = active ? i : 0;
+  const int  lane   = threadIdx.x & 63;
+
+  // ---- the cell's geometry, once for all members of the group
+  int32_t id[S], bt[S];
+  double  cn[S], sn[S], coef[S];
+  int64_t c = 0;
+  // The bed elevations -- row S the cell's own, row s its neighbour's through slot s -- wait in LDS, a column per thread (each
+  // thread reads back only what it wrote: no barrier), and are read through a volatile pointer where an interior slot needs
+  // them.  Held in registers they are loop invariants, and so is everything hr_reconstruct derives from them alone: hipcc then
+  // carries zl, zr, max(zl, zr) and two comparison masks per slot across the member loop -- 24 VGPRs and 16 SGPRs with S = 4,
+  // which spills SGPRs.
+  __shared__ double s_z[S + 1][BLOCK];
+  volatile double  *zs = &s_z[0][threadIdx.x];
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    id[s] = NBR_EMPTY;
+    bt[s] = 0;
+    cn[s] = sn[s] = coef[s] = 0.0;
+  }
+  if (active) {
+    const int32_t *nbr = RDY_COLD(a, nbr), *btype = RDY_COLD(a, btype);
+    const double  *cn_ = RDY_COLD(a, cn), *sn_ = RDY_COLD(a, sn);
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      id[s]   = nbr[s * a.stride + o];
+      cn[s]   = cn_[s * a.stride + o];
+      sn[s]   = sn_[s * a.stride + o];
+      coef[s] = RDY_LD(&a.coef[s * a.stride + o]);
+    }
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      if (id[s] >= 0) zs[s * BLOCK] = a.zc_local[id[s] & NBR_MASK];
+      else if (id[s] != NBR_EMPTY) bt[s] = btype[-1 - id[s]];
+    }
+    c             = a.o2l ? a.o2l[o] : o;
+    zs[S * BLOCK] = a.zc_local[c];
+  }
+  const int32_t *pos    = RDY_COLD(a, pos);
+  const int      m0     = blockIdx.y * t.per_group;
+  const int      m1     = min(t.n_members, m0 + t.per_group);
+  const int      bucket = blockIdx.x * ENSEMBLE_WAVES + (threadIdx.x >> 6);
+
+#pragma unroll 1
+  for (int m = m0; m < m1; ++m) {
+    const double  dt = t.dts[m];
+    const double *um = u + (int64_t)m * t.u_stride;
+    double        best      = 0.0;  // largest Courant number of this cell's edges (> 0 only)
+    int           best_slot = -1;
+    if (active) {
+      const double      h    = um[3 * c + 0];
+      const double      hu   = um[3 * c + 1];
+      const double      hv   = um[3 * c + 2];
+      const RiemannSide self = riemann_side(h, hu, hv, a.tiny_h, a.h_anuga_sq);
+      RiemannSide       self_hr = self;  // interior edges: the HR operator's own cell
+      hr_velocity_rule(self_hr, a.tiny_h);
+      double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0;
+#pragma unroll
+      for (int s = 0; s < S; ++s) {
+        const int32_t nid = id[s];
+        if (nid == NBR_EMPTY) continue;  // a triangle in the 4-slot layout, or an outer edge that belongs to no boundary
+        const double cfac = fabs(coef[s]);  // len / area_self: the max over an edge's two cells is len / min(area_l, area_r)
+        if (nid >= 0) {
+          const int64_t n     = nid & NBR_MASK;
+          RiemannSide   other = riemann_side(um[3 * n + 0], um[3 * n + 1], um[3 * n + 2], a.tiny_h, a.h_anuga_sq);
+          hr_velocity_rule(other, a.tiny_h);
+          const bool  self_left = coef[s] < 0.0;
+          RiemannSide L, R, Lr, Rr;
+          orient_sides(self_hr, other, self_left, L, R);
+          const double z_self = zs[S * BLOCK], z_nbr = zs[s * BLOCK];
+          hr_reconstruct(L, R, self_left ? z_self : z_nbr, self_left ? z_nbr : z_self, Lr, Rr);
+          const RoeFlux fl = roe_flux(Lr, Rr, sn[s], cn[s]);
+          if (!(R.h < a.tiny_h && L.h < a.tiny_h)) {
+            if (Lr.h > a.tiny_h || Rr.h > a.tiny_h) {
+              acc0 += fl.f0 * coef[s];
+              acc1 += fl.f1 * coef[s];
+              acc2 += fl.f2 * coef[s];
+              const double cnum = fl.amax * cfac * dt;
+              if (cnum > best) {
+                best      = cnum;
+                best_slot = s;
+              }
+            }
+            const double h_rec = self_left ? Lr.h : Rr.h;
+            const double corr  = 0.5 * GRAVITY * (h * h - h_rec * h_rec);
+            acc1 += corr * cn[s] * coef[s];
+            acc2 += corr * sn[s] * coef[s];
+          }
+        } else {
+          const int64_t      k  = (int64_t)m * t.k_stride + 3 * (int64_t)(-1 - nid);
+          const BoundaryFlux bf = boundary_flux(bt[s], true, self, t.bvalues + k, sn[s], cn[s], a.tiny_h, a.h_anuga_sq);
+          t.bflux[k + 0]        = bf.flux.f0;  // boundary_fluxes[b], swe_petsc.c:574
+          t.bflux[k + 1]        = bf.flux.f1;
+          t.bflux[k + 2]        = bf.flux.f2;
+          if (bf.wet) {
+            acc0 += bf.flux.f0 * coef[s];
+            acc1 += bf.flux.f1 * coef[s];
+            acc2 += bf.flux.f2 * coef[s];
+            const double cnum = bf.flux.amax * cfac * dt;
+            if (cnum > best) {
+              best      = cnum;
+              best_slot = s;
+            }
+          }
+        }
+      }
+      // sources on the pre-source sums (src/operator.c:663) without the bed slope, then the stores
+      const int64_t r = (int64_t)m * a.n_owned + o;
+      double        bedx, bedy, tbx, tby;
+      cell_source<SRC>(a, dt, h, hu, hv, acc1, acc2, 0.0, 0.0, RDY_LD(&t.mannings[r]), bedx, bedy, tbx, tby);
       const double F0 = acc0 + RDY_LD(&t.extsrc[3 * r + 0]);
       const double F1 = acc1 + (-bedx - tbx + RDY_LD(&t.extsrc[3 * r + 1]));
       const double F2 = acc2 + (-bedy - tby + RDY_LD(&t.extsrc[3 * r + 2]));

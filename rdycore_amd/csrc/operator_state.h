@@ -248,6 +248,7 @@ struct EnsembleState {
   DevBuf<int32_t>            blk_pos;
   DevBuf<DeviceCourant>      d_courant;   // [B]
   std::vector<RDyHipCourant> courant;     // [B] what rdyhip_ensemble_update_diagnostics read last
+  bool                       hr = false;  // enabled by rdyhip_ens_hr_enable: the evaluations run ensemble_hr_kernel
   size_t bytes() const {
     return mannings.bytes() + extsrc.bytes() + bvalues.bytes() + bflux.bytes() + blk_max.bytes() + blk_pos.bytes() + d_courant.bytes();
   }

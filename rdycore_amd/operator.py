@@ -644,11 +644,24 @@ class Operator:
     # -- ensembles (src/ensemble.c): B members on this mesh, state [B, num_cells, 3], one launch per evaluation ---------------------
     num_members = 0
 
-    def enable_ensemble(self, num_members: int):
+    def enable_ensemble(self, num_members: int, well_balancing: int = WELL_BALANCING_NONE):
         """rdyhip_ensemble_enable: `num_members` (1..64) members, each starting with the operator's current Manning's n, external
-        source and boundary values; a member then overrides only what differs"""
-        _lib.check(_lib.load().rdyhip_ensemble_enable(self._h, int(num_members)))
+        source and boundary values; a member then overrides only what differs.  well_balancing=WELL_BALANCING_HR:
+        rdyhip_ens_hr_enable, the same on an operator created with hydrostatic reconstruction (every ensemble call then runs
+        ensemble_hr_kernel)"""
+        if well_balancing == WELL_BALANCING_HR:
+            _lib.check(_lib.load().rdyhip_ens_hr_enable(self._h, int(num_members)))
+        elif well_balancing == WELL_BALANCING_NONE:
+            _lib.check(_lib.load().rdyhip_ensemble_enable(self._h, int(num_members)))
+        else:
+            raise ValueError(f"well_balancing is WELL_BALANCING_NONE or WELL_BALANCING_HR, not {well_balancing}")
         self.num_members = int(num_members)
+
+    def ensemble_well_balancing(self) -> int:
+        """rdyhip_ens_hr_info: WELL_BALANCING_HR after enable_ensemble(..., well_balancing=WELL_BALANCING_HR), else WELL_BALANCING_NONE"""
+        wb = C.c_int32()
+        _lib.check(_lib.load().rdyhip_ens_hr_info(self._h, C.byref(wb)))
+        return wb.value
 
     def ensemble_info(self) -> int:
         """rdyhip_ensemble_info: the number of members, 0: not enabled"""
