@@ -1074,6 +1074,97 @@ int rdyhip_ensemble_get_boundary_fluxes(RDyHipOperator op, int32_t member, int32
 int rdyhip_ensemble_update_diagnostics(RDyHipOperator op, void *stream);
 int rdyhip_ensemble_get_diagnostics(RDyHipOperator op, RDyHipCourant *courant /* [B] */);
 
+/* ---- ensemble output: read-out, error sums, output means, observation series and statistics of the [B][num_cells][3] state --------
+ * What the sections "state read-out", "time-averaged output fields" and "time series on the device" above do for one [cell][3]
+ * state, for all B members of an ensemble in ONE launch per call (csrc/ens_output_kernels.h) instead of B launches and B blocking
+ * round trips on the members' slices, and the per-cell statistics over the members, which the per-member calls cannot form without
+ * copying B states to the host.  The reference runs every member as a simulation of its own (src/ensemble.c:5-84), so each member's
+ * output is the reference's own:
+ *   rdyhip_ens_state_planes / _read_*   RDyGetOwnedCell{Heights,XMomenta,YMomenta} (src/rdydata.c:171-205) of every member
+ *   rdyhip_ens_error_sums / _get        the rank-local loops of RDyMMSComputeErrorNorms (src/rdymms.c:869-880) of every member
+ *   rdyhip_ens_output_mean_*            AccumulateOutputVar / ComputeMean / ResetOutputVar (src/xdmf_output.c:196-241, 436-504)
+ *   rdyhip_ens_series_*                 WriteObservations (src/time_series.c:399-402, 530-564) of every member
+ *   rdyhip_ens_stats                    no counterpart: mean, minimum and maximum over the members (the inundation envelope)
+ * Every call needs an enabled ensemble of either family (rdyhip_ensemble_enable or rdyhip_ens_hr_enable; after the enable the
+ * family makes no difference): a null operator is reported first, "the ensemble is not enabled" next, every other argument error
+ * before any device call, all as RDYHIP_ERR_USER.  u_local is device memory [B][num_cells][3], member-major, as
+ * rdyhip_ensemble_rhs_function takes it; loc(o) is the local cell of owned cell o (the operator's own table where the owned cells
+ * are not the first rows).  A rank that owns nothing launches nothing and succeeds, while times and record counts still advance.
+ * Device memory, counted in RDyHipLayoutInfo.device_bytes as soon as it is allocated and freed by rdyhip_destroy, which waits for a
+ * copy that is still in flight (B members, o = num_owned_cells, S sites, G = min(ceil(o / RDYHIP_ERROR_SUMS_BLOCK),
+ * RDYHIP_ERROR_SUMS_MAX_WORKGROUPS)):
+ *   the read-out     8 B k o bytes for the widest mask (k bits) begun so far; rdyhip_ens_state_planes writes the caller's memory
+ *   the error sums   80 B (G + 1) bytes at the first call, and the area table 8 o + the 80 (G + 1) bytes of rdyhip_error_sums if
+ *                    that has not been called yet (they are shared with it and counted once)
+ *   the means        24 B o bytes per enabled variable
+ *   the series       24 B S capacity + 4 S bytes
+ *   the statistics   none
+ *
+ * `comps` is a mask of RDYHIP_COMPONENT_* (1..7), `comp` exactly one of them, `member` in [0, B).
+ *   - rdyhip_ens_state_planes, the device form: ONE launch on `stream`.  d_planes[m][k][o] = u_local[m][loc(o)][c_k], k over the set
+ *     bits c_k of `comps` ascending; d_planes is device memory [B][popcount(comps)][num_owned_cells].  Values move as 64-bit
+ *     patterns: -0.0, NaN payloads and denormals survive.  Member m's planes are rdyhip_state_planes of member m's slice.
+ *   - rdyhip_ens_state_read_begin / _ready / _wait / _get / _ptr: the state machine of rdyhip_state_read_* rule for rule -- the
+ *     same launch into planes the operator owns, an event, ONE device-to-host copy of all B k planes on the operator's copy stream,
+ *     a second event; only _wait blocks; buffers grow only; a begin over a read that has not landed is ordered behind the earlier
+ *     copy and replaces it; _get / _ptr before _wait, or for a component the last begin did not ask for: RDYHIP_ERR_USER;
+ *     size != num_owned_cells: RDYHIP_ERR_ARG_SIZ -- with planes, pinned memory and events of its own: the SWE read-out of the same
+ *     operator may be in flight at the same time and is never disturbed.
+ *   - rdyhip_ens_error_sums / _get: rdyhip_error_sums for all members in two launches; d_exact is device memory
+ *     [B][num_owned_cells][3] or NULL; `out` of _get is [B].  The partial kernel runs on a (G, B) grid, the finalize kernel with
+ *     workgroup m for member m, then B x 80 bytes go into pinned memory behind an event; _get is the only blocking call.  The
+ *     lane-to-cell assignment, the order of every fold and the three operations per component are those of rdyhip_error_sums:
+ *     member m's record is the SAME BITS rdyhip_error_sums gives for member m's slice (and its exact slice).  The result of
+ *     rdyhip_error_sums on the same operator is left as it was.  NaN: as rdyhip_error_sums.
+ *   - rdyhip_ens_output_mean_*: per enabled variable (`vars`: RDYHIP_OUTPUT_* bits) one accumulator [B][num_owned_cells][3] and one
+ *     accumulated time per member, kept on the host.  _accumulate: `dts` is a host array [B], read at the call; ONE launch for all
+ *     members and all of `vars`.  Per member m: the solution, acc = fma(dts[m], u_solution[m][loc(o)][c], acc); the primitive
+ *     variables (h, u, v) formed in the launch from u_primitive[m][loc(o)] by the arithmetic with which the SWE kernels store them
+ *     and rdyhip_output_mean_accumulate derives them -- the same bits; there is no hidden "state of the last evaluation": the
+ *     caller passes the array the evaluation saw, after a fused Euler step its input; the sources, member m's own external source
+ *     [num_owned_cells][3] (rdyhip_ensemble_set_external_source), read at the call's place in `stream`.  Where u_solution ==
+ *     u_primitive the row is read once; either may be NULL when its variable is not in `vars`.  Each member's time advances by
+ *     its own dts[m].  _get: d_mean (device, [B][num_owned_cells][3]) = accumulator x (1 / accumulated time of member m), the
+ *     reciprocal formed on the host as rdyhip_output_mean_get forms it; accumulated_times is a host array [B] or NULL; a member
+ *     with no accumulated time: RDYHIP_ERR_USER, nothing is launched and nothing written.  _reset: accumulators and all B times of
+ *     `vars` back to zero.  _time: accumulated_times is a host array [B].  A variable that is not enabled, unknown bits, more or
+ *     less than one bit where one variable is asked for, a null array where one is needed: RDYHIP_ERR_USER.  A second _enable
+ *     keeps an accumulator's content.
+ *   - rdyhip_ens_series_*: the semantics of RDYHIP_SERIES_OBSERVATIONS for all members at once -- sites are owned-cell ids, shared
+ *     by the members and range-checked on the host; repeats are allowed; num_sites == 0 is valid; _record (`times`: host array [B],
+ *     one time per member, read at the call) is ONE launch that appends a record [B][S][3] to the log [capacity][B][S][3]; a full
+ *     log is RDYHIP_ERR_USER with nothing launched; a second enable is RDYHIP_ERR_USER; _read (host arrays, times [count][B],
+ *     values [count][B][S][3]) is the only blocking call; _clear empties the log.
+ *     There is no boundary-flux series for ensembles: the ensemble keeps no accumulated boundary-flux array (a stated difference
+ *     above), so there is nothing to record; a member's instantaneous fluxes are rdyhip_ensemble_get_boundary_fluxes.
+ *   - rdyhip_ens_stats: ONE launch, one lane per owned cell, which finds loc(o) once and walks the members.  d_stats is device
+ *     memory [popcount(comps)][3][num_owned_cells]; for the k-th component c_k and x_m = u_local[m][loc(o)][c_k] the three planes are
+ *       mean  s = x_0; s = s + x_m for m = 1 .. B-1 in that order; then s * (1.0 / B), the reciprocal formed on the host
+ *       min   r = x_0; r = (x_m < r) ? x_m : r in member order
+ *       max   r = x_0; r = (x_m > r) ? x_m : r in member order
+ *     Comparisons, not fmin / fmax: of values that compare equal (a tie; +0.0 and -0.0) the EARLIER member's bits are kept; a NaN
+ *     in a later member never replaces the running value; a NaN in member 0 stays to the end.  A NaN in any member makes the mean
+ *     NaN.  The result is the same bits on every run. */
+int rdyhip_ens_state_planes(RDyHipOperator op, int32_t comps, const double *u_local, double *d_planes /* [B][k][owned] */, void *stream);
+int rdyhip_ens_state_read_begin(RDyHipOperator op, int32_t comps, const double *u_local, void *stream);
+int rdyhip_ens_state_read_ready(RDyHipOperator op, int32_t *ready);
+int rdyhip_ens_state_read_wait(RDyHipOperator op);
+int rdyhip_ens_state_read_get(RDyHipOperator op, int32_t member, int32_t comp, int32_t size, double *values /* host */);
+int rdyhip_ens_state_read_ptr(RDyHipOperator op, int32_t member, int32_t comp, const double **pinned_values);
+int rdyhip_ens_error_sums(RDyHipOperator op, const double *u_local, const double *d_exact /* [B][owned][3] or NULL */, void *stream);
+int rdyhip_ens_error_sums_get(RDyHipOperator op, RDyHipErrorSums *out /* [B] */);
+int rdyhip_ens_output_mean_enable(RDyHipOperator op, int32_t vars);
+int rdyhip_ens_output_mean_accumulate(RDyHipOperator op, int32_t vars, const double *dts /* host [B] */, const double *u_solution, const double *u_primitive, void *stream);
+int rdyhip_ens_output_mean_get(RDyHipOperator op, int32_t var, double *d_mean /* [B][owned][3] */, double *accumulated_times /* host [B] or NULL */, void *stream);
+int rdyhip_ens_output_mean_reset(RDyHipOperator op, int32_t vars, void *stream);
+int rdyhip_ens_output_mean_time(RDyHipOperator op, int32_t var, double *accumulated_times /* host [B] */);
+int rdyhip_ens_series_enable(RDyHipOperator op, int32_t num_sites, const int32_t *owned_cell_ids /* host */, int32_t capacity);
+int rdyhip_ens_series_record(RDyHipOperator op, const double *times /* host [B] */, const double *u_local, void *stream);
+int rdyhip_ens_series_info(RDyHipOperator op, int32_t *entries, int32_t *count, int32_t *capacity);
+int rdyhip_ens_series_read(RDyHipOperator op, int32_t first, int32_t count, double *times /* host [count][B] */, double *values /* host [count][B][S][3] */, void *stream);
+int rdyhip_ens_series_clear(RDyHipOperator op);
+int rdyhip_ens_stats(RDyHipOperator op, int32_t comps, const double *u_local, double *d_stats /* [k][3][owned] */, void *stream);
+
 /* ---- introspection ----------------------------------------------------------
  * numbers describing the device layout, for DESIGN.md / bench.py */
 typedef struct {

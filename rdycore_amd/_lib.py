@@ -181,6 +181,25 @@ SYMBOLS = {
     "rdyhip_ensemble_get_diagnostics": (C.c_int, [_H, C.POINTER(RDyHipCourant)]),
     "rdyhip_ens_hr_enable": (C.c_int, [_H, C.c_int32]),
     "rdyhip_ens_hr_info": (C.c_int, [_H, c_int32_p]),
+    "rdyhip_ens_state_planes": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rdyhip_ens_state_read_begin": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p]),
+    "rdyhip_ens_state_read_ready": (C.c_int, [_H, c_int32_p]),
+    "rdyhip_ens_state_read_wait": (C.c_int, [_H]),
+    "rdyhip_ens_state_read_get": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, c_double_p]),
+    "rdyhip_ens_state_read_ptr": (C.c_int, [_H, C.c_int32, C.c_int32, C.POINTER(c_double_p)]),
+    "rdyhip_ens_error_sums": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rdyhip_ens_error_sums_get": (C.c_int, [_H, C.POINTER(RDyHipErrorSums)]),
+    "rdyhip_ens_output_mean_enable": (C.c_int, [_H, C.c_int32]),
+    "rdyhip_ens_output_mean_accumulate": (C.c_int, [_H, C.c_int32, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rdyhip_ens_output_mean_get": (C.c_int, [_H, C.c_int32, C.c_void_p, c_double_p, C.c_void_p]),
+    "rdyhip_ens_output_mean_reset": (C.c_int, [_H, C.c_int32, C.c_void_p]),
+    "rdyhip_ens_output_mean_time": (C.c_int, [_H, C.c_int32, c_double_p]),
+    "rdyhip_ens_series_enable": (C.c_int, [_H, C.c_int32, c_int32_p, C.c_int32]),
+    "rdyhip_ens_series_record": (C.c_int, [_H, c_double_p, C.c_void_p, C.c_void_p]),
+    "rdyhip_ens_series_info": (C.c_int, [_H, c_int32_p, c_int32_p, c_int32_p]),
+    "rdyhip_ens_series_read": (C.c_int, [_H, C.c_int32, C.c_int32, c_double_p, c_double_p, C.c_void_p]),
+    "rdyhip_ens_series_clear": (C.c_int, [_H]),
+    "rdyhip_ens_stats": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rdyhip_halo_create": (C.c_int, [_H, C.c_void_p, C.c_int32, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p, C.POINTER(C.c_void_p)]),
     "rdyhip_halo_destroy": (C.c_int, [C.POINTER(C.c_void_p)]),
     "rdyhip_halo_overlaps": (C.c_int32, [C.c_void_p]),

@@ -254,6 +254,51 @@ struct EnsembleState {
   }
 };
 
+// rdyhip_ens_state_* / _error_sums / _output_mean_* / _series_* / _stats (ens_output_kernels.h): the read-out, the error sums, the
+// output means and the observation series of the [B][cell][3] ensemble state, each what Readout, OutputMeans and Series hold for
+// one state, B times over -- of their own, so that the SWE read-out of the same operator is never disturbed.  The area table of
+// the error sums is Readout::d_area.  Everything is allocated by the first call that needs it (means, series: by their enable).
+struct EnsembleOutput {
+  enum State { NONE, IN_FLIGHT, LANDED };
+  // the getters
+  DevBuf<double> d_planes;            // [B][popcount(comps)][n_owned], room for the widest mask asked for so far
+  double        *h_planes = nullptr;  // pinned, as many doubles as d_planes
+  size_t         h_cap = 0;
+  hipEvent_t     launched = nullptr, done = nullptr;
+  State          state = NONE;
+  int32_t        comps = 0;           // the mask of the last begin
+  // the error sums
+  DevBuf<double> d_records;           // [B][err_wg + 1][10]: every member's workgroup records, then the B results
+  double        *h_sums = nullptr;    // pinned, [B][10] (B x RDyHipErrorSums)
+  hipEvent_t     sums_done = nullptr;
+  State          sums_state = NONE;
+  // the output means: one [B][n_owned][3] accumulator per enabled variable and, per variable, the time every member's spans
+  DevBuf<double>      acc[3];
+  std::vector<double> time[3];        // [B] each
+  // the observation series: `capacity` records of B x entries x 3 doubles, the B times of every record on the host
+  bool                series_enabled = false;
+  int32_t             entries = 0, capacity = 0;
+  DevBuf<double>      d_log;
+  DevBuf<int32_t>     d_sites;        // [entries] local cell of every site
+  std::vector<double> times;          // [records][B]
+  int32_t             records = 0;
+  EnsembleOutput() = default;
+  EnsembleOutput(const EnsembleOutput &) = delete;
+  EnsembleOutput &operator=(const EnsembleOutput &) = delete;
+  ~EnsembleOutput() {
+    if (state == IN_FLIGHT && done) (void)hipEventSynchronize(done);   // the copies write pinned memory
+    if (sums_state == IN_FLIGHT && sums_done) (void)hipEventSynchronize(sums_done);
+    if (h_planes) (void)hipHostFree(h_planes);
+    if (h_sums) (void)hipHostFree(h_sums);
+    if (launched) (void)hipEventDestroy(launched);
+    if (done) (void)hipEventDestroy(done);
+    if (sums_done) (void)hipEventDestroy(sums_done);
+  }
+  size_t bytes() const {
+    return d_planes.bytes() + d_records.bytes() + acc[0].bytes() + acc[1].bytes() + acc[2].bytes() + d_log.bytes() + d_sites.bytes();
+  }
+};
+
 struct RDyHipHalo_s;
 // (the layout's numbers -- n_cells, n_owned, S, K, n_halo, ntiles, ... -- are the base class's, copied from HostLayout::counts)
 struct RDyHipOperator_s : LayoutCounts {
@@ -347,12 +392,13 @@ struct RDyHipOperator_s : LayoutCounts {
   TracerState   tracers;
   TracerOutput  tracer_out;
   EnsembleState ensemble;
+  EnsembleOutput ens_out;
   DiagnosticsRead diag_read[2];   // RDYHIP_DIAGNOSTICS_OPERATOR, RDYHIP_DIAGNOSTICS_ENSEMBLE
 
   int64_t device_bytes = 0;   // what rdyhip_create allocated; rdyhip_layout_info adds the features'
   int64_t feature_bytes() const {
     return (int64_t)(rk4.bytes() + means.bytes() + series[0].bytes() + series[1].bytes() + readout.bytes() + tracers.bytes() + tracer_out.bytes() +
-                     ensemble.bytes());
+                     ensemble.bytes() + ens_out.bytes());
   }
 };
 

@@ -51,6 +51,7 @@
 #include "tracer_kernels.h"
 #include "tracer_output_kernels.h"
 #include "ensemble_kernels.h"
+#include "ens_output_kernels.h"
 #include "operator_state.h"
 
 using namespace rdyhip;
@@ -827,5 +828,6 @@ int rdyhip_layout_info(RDyHipOperator op, RDyHipLayoutInfo *info) {
 #include "tracer_calls.h"
 #include "tracer_output_calls.h"
 #include "ensemble_calls.h"
+#include "ens_output_calls.h"
 #include "diagnostics_calls.h"
 

@@ -753,6 +753,141 @@ class Operator:
         _lib.check(_lib.load().rdyhip_ensemble_get_diagnostics(self._h, c))
         return [CourantNumberDiagnostics(c[m].max_courant_num, c[m].global_edge_id, c[m].global_cell_id) for m in range(self.num_members)]
 
+    # -- ensemble output (rdyhip_ens_state_* / _error_sums / _output_mean_* / _series_* / _stats): the read-out, error sums, output
+    # means, observation series and member statistics of the [B, num_cells, 3] state, every call one launch for all members -------
+    @staticmethod
+    def _mask_bits(comps: int) -> int:
+        return bin(int(comps)).count("1") if 1 <= int(comps) <= 7 else 0
+
+    def _ensemble_per_member(self, values, name: str):
+        d = np.ascontiguousarray(values, dtype=np.float64).ravel()
+        if d.size != self.num_members:
+            raise RDyHipError(83, f"{name} must hold one value per member ({self.num_members}), not {d.size}")
+        return d
+
+    def ensemble_state_planes(self, u_local: torch.Tensor, comps: int) -> torch.Tensor:
+        """rdyhip_ens_state_planes: [B, popcount(comps), owned] device tensor, plane [m, k] = the k-th component of `comps`
+        (ascending) of member m's owned cells, bit for bit; one launch on the current stream"""
+        self._check_ensemble_state(u_local, "u_local", self.mesh.num_cells)
+        out = torch.empty((self.num_members, self._mask_bits(comps), self.mesh.num_owned_cells), dtype=torch.float64, device="cuda")
+        _lib.check(_lib.load().rdyhip_ens_state_planes(self._h, int(comps), _ptr(u_local), _ptr(out), _stream()))
+        return out
+
+    def ensemble_read_state_begin(self, u_local: torch.Tensor, comps: int):
+        """rdyhip_ens_state_read_begin: as read_state_begin, for all members in one launch and one copy, with buffers of its own"""
+        self._check_ensemble_state(u_local, "u_local", self.mesh.num_cells)
+        _lib.check(_lib.load().rdyhip_ens_state_read_begin(self._h, int(comps), _ptr(u_local), _stream()))
+
+    def ensemble_read_state_ready(self) -> bool:
+        """rdyhip_ens_state_read_ready: the copy of the last ensemble_read_state_begin has finished (an event query)"""
+        out = C.c_int32()
+        _lib.check(_lib.load().rdyhip_ens_state_read_ready(self._h, C.byref(out)))
+        return bool(out.value)
+
+    def ensemble_read_state(self, member: int, comp: int) -> np.ndarray:
+        """rdyhip_ens_state_read_wait + _get: waits for the copy of the last ensemble_read_state_begin (for that alone) and returns
+        component `comp` (exactly one COMPONENT_*) of member `member`'s owned cells as a numpy array"""
+        lib = _lib.load()
+        _lib.check(lib.rdyhip_ens_state_read_wait(self._h))
+        out = np.empty(self.mesh.num_owned_cells)
+        _lib.check(lib.rdyhip_ens_state_read_get(self._h, int(member), int(comp), int(out.size),
+                                                 out.ctypes.data_as(_lib.c_double_p) if out.size else None))
+        return out
+
+    def ensemble_error_sums(self, u_local: torch.Tensor, exact: Optional[torch.Tensor] = None) -> list:
+        """rdyhip_ens_error_sums + _get: one dict of Operator.error_sums per member, of u_local[m] - exact[m] over the owned cells
+        (`exact`: [B, owned, 3] device tensor; None: zeros); two launches for all members; member m's dict holds the bits
+        error_sums gives for member m's slice"""
+        self._check_ensemble_state(u_local, "u_local", self.mesh.num_cells)
+        self._check_ensemble_state(exact, "exact", self.mesh.num_owned_cells, optional=True)
+        lib = _lib.load()
+        _lib.check(lib.rdyhip_ens_error_sums(self._h, _ptr(u_local), _ptr(exact) if exact is not None else None, _stream()))
+        s = (_lib.RDyHipErrorSums * max(self.num_members, 1))()
+        _lib.check(lib.rdyhip_ens_error_sums_get(self._h, s))
+        return [{"l1": np.array(s[m].l1[:]), "l2_squared": np.array(s[m].l2_squared[:]), "linf": np.array(s[m].linf[:]), "area": float(s[m].area)}
+                for m in range(self.num_members)]
+
+    def ensemble_enable_output_means(self, vars: int):
+        """rdyhip_ens_output_mean_enable: a zeroed [B, owned, 3] accumulator for each of OUTPUT_* in `vars` that has none yet"""
+        _lib.check(_lib.load().rdyhip_ens_output_mean_enable(self._h, int(vars)))
+
+    def ensemble_accumulate_output_means(self, vars: int, dts, u_solution: Optional[torch.Tensor] = None,
+                                         u_primitive: Optional[torch.Tensor] = None):
+        """rdyhip_ens_output_mean_accumulate: all of `vars` of all members in one launch on the current stream, member m weighted
+        with dts[m] -- the solution from `u_solution`, the primitive variables formed from `u_primitive` (the state the evaluation
+        saw: after a fused Euler step its input), the sources from the members' own; each state [B, num_cells, 3], needed only
+        with its variable"""
+        d = self._ensemble_per_member(dts, "dts")
+        self._check_ensemble_state(u_solution, "u_solution", self.mesh.num_cells, optional=True)
+        self._check_ensemble_state(u_primitive, "u_primitive", self.mesh.num_cells, optional=True)
+        _lib.check(_lib.load().rdyhip_ens_output_mean_accumulate(self._h, int(vars), d.ctypes.data_as(_lib.c_double_p),
+                                                                _ptr(u_solution) if u_solution is not None else None,
+                                                                _ptr(u_primitive) if u_primitive is not None else None, _stream()))
+
+    def ensemble_output_mean(self, var: int):
+        """rdyhip_ens_output_mean_get: (means [B, owned, 3], accumulated times [B]) of one variable; nothing is reset"""
+        out = torch.empty((self.num_members, self.mesh.num_owned_cells, 3), dtype=torch.float64, device="cuda")
+        t = np.zeros(max(self.num_members, 1))
+        _lib.check(_lib.load().rdyhip_ens_output_mean_get(self._h, int(var), _ptr(out), t.ctypes.data_as(_lib.c_double_p), _stream()))
+        return out, t[:self.num_members]
+
+    def ensemble_reset_output_means(self, vars: int):
+        """rdyhip_ens_output_mean_reset: accumulators and every member's time of `vars` back to zero, on the current stream"""
+        _lib.check(_lib.load().rdyhip_ens_output_mean_reset(self._h, int(vars), _stream()))
+
+    def ensemble_output_mean_time(self, var: int) -> np.ndarray:
+        """rdyhip_ens_output_mean_time: [B] the time every member has accumulated for `var`"""
+        t = np.zeros(max(self.num_members, 1))
+        _lib.check(_lib.load().rdyhip_ens_output_mean_time(self._h, int(var), t.ctypes.data_as(_lib.c_double_p)))
+        return t[:self.num_members]
+
+    def ensemble_enable_observation_series(self, owned_cell_ids, capacity: int):
+        """rdyhip_ens_series_enable: a device log of `capacity` records of every member's state in the cells `owned_cell_ids`
+        (owned-cell indices; a site may repeat)"""
+        ids = np.ascontiguousarray(owned_cell_ids, dtype=np.int32).ravel()
+        arg = ids if ids.size else np.zeros(1, dtype=np.int32)
+        _lib.check(_lib.load().rdyhip_ens_series_enable(self._h, int(ids.size), arg.ctypes.data_as(_lib.c_int32_p), int(capacity)))
+
+    def ensemble_series_record(self, times, u_local: torch.Tensor):
+        """rdyhip_ens_series_record: one record [B, sites, 3] of the state `u_local` appended to the log at the members' `times`
+        ([B]), one launch on the current stream"""
+        t = self._ensemble_per_member(times, "times")
+        self._check_ensemble_state(u_local, "u_local", self.mesh.num_cells)
+        _lib.check(_lib.load().rdyhip_ens_series_record(self._h, t.ctypes.data_as(_lib.c_double_p), _ptr(u_local), _stream()))
+
+    def ensemble_series_info(self) -> dict:
+        """rdyhip_ens_series_info: sites of a record, records in the log, capacity"""
+        e, n, cap = C.c_int32(), C.c_int32(), C.c_int32()
+        _lib.check(_lib.load().rdyhip_ens_series_info(self._h, C.byref(e), C.byref(n), C.byref(cap)))
+        return {"entries": e.value, "count": n.value, "capacity": cap.value}
+
+    def ensemble_series_read(self, first: int = 0, count: Optional[int] = None):
+        """rdyhip_ens_series_read: (times [count, B], values [count, B, sites, 3]) of records [first, first + count) as numpy arrays
+        (count=None: all from `first`); synchronises the current stream"""
+        info = self.ensemble_series_info()
+        if count is None:
+            count = max(info["count"] - int(first), 0)
+        times = np.zeros((max(int(count), 0), self.num_members))
+        values = np.zeros((max(int(count), 0), self.num_members, info["entries"], 3))
+        tp = times.ctypes.data_as(_lib.c_double_p) if times.size else None
+        vp = values.ctypes.data_as(_lib.c_double_p) if values.size else None
+        _lib.check(_lib.load().rdyhip_ens_series_read(self._h, int(first), int(count), tp, vp, _stream()))
+        return times, values
+
+    def ensemble_series_clear(self):
+        """rdyhip_ens_series_clear: the log holds no records"""
+        _lib.check(_lib.load().rdyhip_ens_series_clear(self._h))
+
+    def ensemble_stats(self, u_local: torch.Tensor, comps: int) -> torch.Tensor:
+        """rdyhip_ens_stats: [popcount(comps), 3, owned] device tensor, planes [k, 0..2] = mean, minimum and maximum over the members
+        of the k-th component of `comps` in every owned cell; one launch on the current stream.  The mean adds the members in
+        order and multiplies by 1 / B once; minimum and maximum are comparisons in member order: of equal values (+0.0 and -0.0
+        too) the earlier member's bits stay, a NaN in a later member is passed over, a NaN in member 0 stays."""
+        self._check_ensemble_state(u_local, "u_local", self.mesh.num_cells)
+        out = torch.empty((self._mask_bits(comps), 3, self.mesh.num_owned_cells), dtype=torch.float64, device="cuda")
+        _lib.check(_lib.load().rdyhip_ens_stats(self._h, int(comps), _ptr(u_local), _ptr(out), _stream()))
+        return out
+
     # -- second order: ComputeLeastSquaresGradients for the owned cells (src/operator_fluxes_ceed.c:998-1042)
     def compute_gradients(self, u_local: torch.Tensor, phase: int = PHASE_ALL):
         _lib.check(_lib.load().rdyhip_compute_gradients(self._h, int(phase), _ptr(u_local), _stream()))

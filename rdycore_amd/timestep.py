@@ -300,11 +300,23 @@ class EnsembleEulerStepper:
     steps, member m with its own fixed dts[m], one fused launch per step for all members (rdyhip_ensemble_euler_step), the
     steps ping-ponging between two [B, num_cells, 3] arrays.  Adaptive per-member dt is a follow-up."""
 
-    def __init__(self, op):
+    def __init__(self, op, means: int = 0, series: Optional[TimeSeries] = None):
+        """`means` (OUTPUT_* bits; 0, the default: none of the operator's ensemble output-mean calls is made): the stepper enables
+        the [B, owned, 3] accumulators and, after every step, accumulates with solution = the step's output and primitive
+        variables = the step's input state, member m weighted with the step's dts[m], one launch for all members.  `series` (a
+        TimeSeries; None, the default: no series call is made): its observation sites are enabled, and after every step whose
+        count is a multiple of observation_interval a record of the step's output is appended at the members' times.  There is
+        no boundary-flux series for ensembles, and -- as with TracerEulerStepper -- no monitor call before the first step."""
         self.op = op
         self.step = 0
         self.times = None        # [B] the time every member has reached
         self._own = [None, None]  # the stepper's arrays: the partner of the caller's array, and the partner of that one
+        self.means = int(means)
+        if self.means:
+            op.ensemble_enable_output_means(self.means)
+        self.series = series
+        if series is not None and series.observation_interval:
+            op.ensemble_enable_observation_series(series.observation_sites, series.capacity)
 
     def _partner(self, u: torch.Tensor) -> torch.Tensor:
         """the array the first step from `u` writes: the stepper's first array, or -- when `u` is one of the stepper's own, the
@@ -324,12 +336,30 @@ class EnsembleEulerStepper:
         if self.times is None:
             self.times = np.zeros(d.size)
         cur, nxt = u, self._partner(u)
+        s = self.series
         for _ in range(int(nsteps)):
             self.op.ensemble_euler_step(d, cur, nxt)
+            if self.means:
+                self.op.ensemble_accumulate_output_means(self.means, d, nxt, cur)   # solution: the step's output; primitive: its input
             cur, nxt = nxt, cur
             self.times = self.times + d
             self.step += 1
+            if s is not None and s.observation_interval and self.step % s.observation_interval == 0:
+                self.op.ensemble_series_record(self.times, cur)
         return cur
+
+    def series_read(self, clear: bool = False):
+        """the observation log, (times [records, B], values [records, B, sites, 3]); `clear`: the log then starts empty"""
+        out = self.op.ensemble_series_read()
+        if clear:
+            self.op.ensemble_series_clear()
+        return out
+
+    def output_mean(self, var: int):
+        """(means [B, owned, 3], accumulated times [B]) of one variable; its next window starts empty"""
+        mean, t = self.op.ensemble_output_mean(var)
+        self.op.ensemble_reset_output_means(var)
+        return mean, t
 
 
 class TracerEulerStepper:
