@@ -163,6 +163,10 @@
         walk_t           = hw->a.tile_walk;
         ctr_t            = load_uniform(&hw->a.cold->tile_draw, 0);
       }
+      // ... and the owned -> local map the batch looks the cells of the tile after the next up in: asked for with them, a
+      // phase 0 ahead of its use.  (Held for the launch, the pointer and its null test are SGPRs that the tie path of phase 2
+      // has to restore from VGPR lanes.)
+      const int32_t *const o2l_hot = hot_kernargs()->a.o2l;
       const int  ne = td.ne(), nh = td.nh();
       const int  o      = td.c_off + tid;
       const bool active = tid < td.nc();
@@ -214,7 +218,7 @@
           td2   = tile_desc(tile2);
           if (tid < td2.nh()) hid2 = *lane_ptr(a.hcells + (int64_t)td2.h_off, lane_bytes(tid, 2));
           const int o2 = td2.c_off + tid;
-          c2           = (a.o2l && tid < td2.nc()) ? a.o2l[o2] : o2;
+          c2           = (o2l_hot && tid < td2.nc()) ? o2l_hot[o2] : o2;
         }
       }
       // (b) the next tile's cell states, edge records and per-cell streams
@@ -344,31 +348,60 @@
         }
         bool      tie      = false;  // a slot of this cell met the thread's running Courant maximum to the last bit
         const int rec_in   = trk.rec;
+        // The LDS reads of phase 2 in ONE batch with one wait: the S wave speeds, the 3 S fluxes and the lane's own depth and
+        // velocities.  All addresses are known once the slot words are in registers; read where they are used, each value cost
+        // a round trip of its own (the guards below sit between them), ten in series for a triangle's twelve values.  An
+        // empty slot reads the last record's entry of each plane (in bounds: a tile has <= TILE_MAX_REC records); nobody looks
+        // at what it gets.  The guards and the sums stay what they were.
+        //      The lane's own momenta are NOT in the batch: cell_results reads them where it did.  As values of another block,
+        // hipcc contracts the friction term's u u + v v the other way round -- fma(u, u, v v) for fma(v, v, u u) -- and a
+        // cell in ten thousand gets another last bit.
+        uint32_t refs[S];
+        double   ams[S], e0[S], e1[S], e2[S];
 #pragma unroll
         for (int s = 0; s < S; ++s) {
-          uint32_t ref;
           if (S == 3) {
-            ref = (cur.r0 >> (10 * s)) & 0x3FF;
-            if (ref == REF3_EMPTY) continue;
+            refs[s] = (cur.r0 >> (10 * s)) & 0x3FF;
           } else {
             const uint32_t w = (s < 2) ? cur.r0 : cur.r1;
-            ref              = (s & 1) ? (w >> 16) : (w & 0xFFFFu);
-            if (ref == SLOT_EMPTY) continue;
+            refs[s]          = (s & 1) ? (w >> 16) : (w & 0xFFFFu);
           }
-          const double am = eam[ref];
+          const uint32_t j = refs[s] & (uint32_t)(TILE_MAX_REC - 1);
+          ams[s]           = eam[j];
+          e0[s]            = ef0[j];
+          if (HR) {
+            const bool left = __builtin_signbit(cur.coef[s]);  // this cell is the edge's left (k = -len/area, -0.0 for a degenerate edge) or right cell
+            e1[s]           = (left ? ef1 : efr1)[j];
+            e2[s]           = (left ? ef2 : efr2)[j];
+          } else {
+            e1[s] = ef1[j];
+            e2[s] = ef2[j];
+          }
+        }
+        const double self_h = sd_h[tid], self_u = sd_u[tid], self_v = sd_v[tid];
+        asm volatile("" ::"v"(ams[0]), "v"(ams[1]), "v"(ams[2]), "v"(ams[S - 1]), "v"(e0[0]), "v"(e0[1]), "v"(e0[2]), "v"(e0[S - 1]), "v"(e1[0]),
+                     "v"(e1[1]), "v"(e1[2]), "v"(e1[S - 1]), "v"(e2[0]), "v"(e2[1]), "v"(e2[2]), "v"(e2[S - 1]), "v"(self_h), "v"(self_u),
+                     "v"(self_v));
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+          const uint32_t ref = refs[s];
+          if (ref == (S == 3 ? REF3_EMPTY : (uint32_t)SLOT_EMPTY)) continue;
+          const double am = ams[s];
           const double k  = cur.coef[s];
           if (HR) {
             // a dry-dry edge (am == -1) carries zero Roe flux here but still its pressure correction
-            const bool left = __builtin_signbit(k);  // this cell is the edge's left (k = -len/area, -0.0 for a degenerate edge) or right cell
-            acc0 += ef0[ref] * k;
-            acc1 += (left ? ef1 : efr1)[ref] * k;
-            acc2 += (left ? ef2 : efr2)[ref] * k;
-          } else if (am != -1.0) {
-            acc0 += ef0[ref] * k;
-            acc1 += ef1[ref] * k;
-            acc2 += ef2[ref] * k;
+            acc0 += e0[s] * k;
+            acc1 += e1[s] * k;
+            acc2 += e2[s] * k;
           }
           if (am != -1.0) {
+            // (in the arm of the Courant compares: in an arm of their own, now that they load nothing, hipcc runs the three
+            // fma for every slot and picks with six v_cndmask)
+            if (!HR) {
+              acc0 += e0[s] * k;
+              acc1 += e1[s] * k;
+              acc2 += e2[s] * k;
+            }
             // len/area_self: the max over an edge's two cells is len / min(area_l, area_r) (swe_petsc.c:289)
             const double cnum = am * fabs(k) * dt;
             tie |= cnum == trk.best;
@@ -394,16 +427,13 @@
           int first = -1;  // the first slot of this cell at the running maximum: the only one that can come before the incumbent
 #pragma unroll
           for (int s = 0; s < S; ++s) {
-            uint32_t ref;
-            if (S == 3) {
-              ref = (cur.r0 >> (10 * s)) & 0x3FF;
-              if (ref == REF3_EMPTY) continue;
-            } else {
-              const uint32_t w = (s < 2) ? cur.r0 : cur.r1;
-              ref              = (s & 1) ? (w >> 16) : (w & 0xFFFFu);
-              if (ref == SLOT_EMPTY) continue;
-            }
-            const double am = eam[ref];
+            const uint32_t ref = refs[s];
+            if (ref == (S == 3 ? REF3_EMPTY : (uint32_t)SLOT_EMPTY)) continue;
+            // the batch's value, nothing has written the plane since: no round trip here either.  (Taken as a value of its own:
+            // left to merge this path's products with the slot loop's, hipcc keeps those alive across the branch for a path
+            // almost no tile takes.)
+            double am = ams[s];
+            asm volatile("" : "+v"(am));
             if (first < 0 && am != -1.0 && am * fabs(cur.coef[s]) * dt == trk.best) first = (int)ref;
           }
           if (first >= 0) courant_resolve_tie(a, trk, td.e_off + first, first >= COURANT_Q ? pos_q : pos_lo);
@@ -411,10 +441,10 @@
         acc_fdiv[0] = acc0;
         acc_fdiv[1] = acc1;
         acc_fdiv[2] = acc2;
-        cell_results<SRC>(a, dt, sd_h[tid], sd_hu[tid], sd_hv[tid], acc0, acc1, acc2, cur.dzdx, cur.dzdy, cur.nman, cur.s0, cur.s1, cur.s2, out);
-        out[3] = sd_h[tid];
-        out[4] = sd_u[tid];
-        out[5] = sd_v[tid];
+        cell_results<SRC>(a, dt, self_h, sd_hu[tid], sd_hv[tid], acc0, acc1, acc2, cur.dzdx, cur.dzdy, cur.nman, cur.s0, cur.s1, cur.s2, out);
+        out[3] = self_h;
+        out[4] = self_u;
+        out[5] = self_v;
         if (HR_STAGED_VEL && out[3] == a.tiny_h) {  // primitive variables: zero BELOW tiny_h (swe_petsc.c:788-791), see hr_velocity_rule
           const RiemannSide s = riemann_side(out[3], sd_hu[tid], sd_hv[tid], a.tiny_h, a.h_anuga_sq);
           out[4] = s.u;

@@ -13,7 +13,8 @@ sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 
 ARGS = {
-    "c3": [], "hr": ["--hr"], "xq": ["--source", "implicit_xq2018"], "c2": ["--workload", "c2"], "quads": ["--workload", "dambreak_quads"],
+    "c3": [], "hr": ["--hr"], "xq": ["--source", "implicit_xq2018"], "c2": ["--workload", "c2"], "c2_hr": ["--workload", "c2", "--hr"],
+    "c2_xq": ["--workload", "c2", "--source", "implicit_xq2018"], "quads": ["--workload", "dambreak_quads"],
     "c5": ["--workload", "c5", "--emulate-world", "8", "--emulate-rank", "3"], "so": ["--second-order"],
     "so_quads": ["--second-order", "--workload", "dambreak_quads"], "houston": ["--workload", "houston_refined"],
     "houston_hr": ["--workload", "houston_refined", "--hr"], "houston_so": ["--workload", "houston_refined", "--second-order"],

@@ -118,6 +118,42 @@ def static_ops(lines, pat, ops=LANE_OPS):
     return sum(b.ops[o] for b in blocks(lines, pat) for o in ops)
 
 
+def loop_code(lines, pat):
+    """The hot loop's instructions in program order (labels and directives dropped)."""
+    body = kernel_body(lines, pat)
+    bl = blocks(lines, pat)
+    head, back = hot_loop(bl)
+    first = next(i for i, l in enumerate(body) if l.startswith(bl[head].label + ":"))
+    after = bl[back + 1].label if back + 1 < len(bl) and bl[back + 1].label.startswith(".LBB") else None
+    last = next((i for i, l in enumerate(body) if after and l.startswith(after + ":")), len(body))
+    code = [l.split(";")[0].strip() for l in body[first:last]]
+    return [t for t in code if t and not t.startswith(".") and not t.endswith(":")]
+
+
+def lds_round_trips(code):
+    """s_waitcnt instructions that carry an lgkmcnt and have at least one ds_read issued since the previous such wait: the LDS
+    round trips a wave pays one after the other on a stretch of code (static, cold arms included)."""
+    n, pending = 0, False
+    for t in code:
+        op = t.split()[0]
+        if op.startswith("ds_read"):
+            pending = True
+        elif op == "s_waitcnt" and "lgkmcnt" in t:
+            n += pending
+            pending = False
+    return n
+
+
+def phase2_round_trips(lines, pat):
+    """LDS round trips of phase 2's reads: from the hot loop's second s_barrier to the first hinted global_load behind it (the
+    next tile's per-cell streams, issued when the cell sum and the cell's results are done)."""
+    code = loop_code(lines, pat)
+    bars = [i for i, t in enumerate(code) if t.split()[0] == "s_barrier"]
+    start = bars[1]
+    end = next(i for i in range(start, len(code)) if code[i].startswith("global_load") and re.search(r"\bnt\b", code[i]))
+    return lds_round_trips(code[start:end])
+
+
 def main(argv):
     args = [a for a in argv if not a.startswith("--")]
     cold = ()

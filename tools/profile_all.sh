@@ -11,6 +11,8 @@ V[c3]=""
 V[hr]="--hr"
 V[xq]="--source implicit_xq2018"
 V[c2]="--workload c2"
+V[c2_hr]="--workload c2 --hr"
+V[c2_xq]="--workload c2 --source implicit_xq2018"
 V[quads]="--workload dambreak_quads"
 V[c5]="--workload c5 --emulate-world 8 --emulate-rank 3"
 V[so]="--second-order"
