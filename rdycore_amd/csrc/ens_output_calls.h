@@ -1,8 +1,8 @@
 // Output of the ensemble state behind the C ABI (rdyhip_ens_state_*, rdyhip_ens_error_sums*, rdyhip_ens_output_mean_*,
 // rdyhip_ens_series_*, rdyhip_ens_stats; kernels: ens_output_kernels.h): the read-out, error sums, output means and observation
-// series of readout_calls.h, output_calls.h and series_calls.h for all B members in one launch each, and the statistics over the
-// members.  Included by rdyhip_api.hip only, after ensemble_calls.h (ensemble_check, ensemble_check_member) and those three
-// (READ_COMPS, popcount3, one_component, sums_reserve, OUT_VARS, output_index).
+// series of readout_calls.h, output_calls.h and series_calls.h for all B members in one launch each, over the same helpers
+// (output_shared.h), and the statistics over the members.  Included by rdyhip_api.hip only, after ensemble_calls.h (ensemble_check,
+// ensemble_check_member) and readout_calls.h (READ_COMPS, one_component).
 #pragma once
 namespace {
 
@@ -21,86 +21,24 @@ int eout_check_member_comp(RDyHipOperator op, int32_t member, int32_t comp) {
   return 0;
 }
 
-const int32_t *eout_o2l(RDyHipOperator op) { return op->prefix ? (const int32_t *)nullptr : op->d_o2l.p; }
 dim3 eout_grid(RDyHipOperator op, int64_t n) { return dim3((unsigned)((n + ENS_OUT_BLOCK - 1) / ENS_OUT_BLOCK), (unsigned)op->ensemble.members); }
 
 int launch_ens_planes(RDyHipOperator op, int32_t comps, const double *u, double *planes, hipStream_t st) {
-  hipLaunchKernelGGL(ens_planes_kernel, eout_grid(op, op->n_owned), dim3(ENS_OUT_BLOCK), 0, st, op->n_owned, eout_o2l(op), (int)comps, popcount3(comps),
+  hipLaunchKernelGGL(ens_planes_kernel, eout_grid(op, op->n_owned), dim3(ENS_OUT_BLOCK), 0, st, op->n_owned, owned_to_local(op), (int)comps, popcount(comps),
                      3 * (int64_t)op->n_cells, (const uint64_t *)u, (uint64_t *)planes);
   HIP_TRY(hipGetLastError());
-  return 0;
-}
-
-// read_reserve (readout_calls.h) for the ensemble read-out's own buffers and events: B x k planes; the copy stream is the operator's
-int eout_read_reserve(RDyHipOperator op, int k) {
-  EnsembleOutput &r = op->ens_out;
-  if (!op->stage.copy) HIP_TRY(hipStreamCreateWithFlags(&op->stage.copy, hipStreamNonBlocking));
-  if (!r.launched) HIP_TRY(hipEventCreateWithFlags(&r.launched, hipEventDisableTiming));
-  if (!r.done) HIP_TRY(hipEventCreateWithFlags(&r.done, hipEventDisableTiming));
-  const size_t need = (size_t)op->ensemble.members * (size_t)k * (size_t)op->n_owned;
-  if (r.d_planes.p && r.d_planes.n >= need && r.h_cap >= need) return 0;
-  if (r.state == EnsembleOutput::IN_FLIGHT) HIP_TRY(hipEventSynchronize(r.done));
-  r.state = EnsembleOutput::NONE;   // whatever had been read lived in the old buffers
-  int rc = r.d_planes.alloc(need);
-  if (rc) return rc;
-  if (r.h_planes) HIP_TRY(hipHostFree(r.h_planes));
-  r.h_planes = nullptr;
-  r.h_cap    = 0;
-  HIP_TRY(hipHostMalloc((void **)&r.h_planes, sizeof(double) * need, hipHostMallocDefault));
-  r.h_cap = need;
-  return 0;
-}
-
-// the state checks of _get and _ptr; *plane = the index of (member, comp) among the planes of the last begin
-int eout_check_landed(RDyHipOperator op, int32_t member, int32_t comp, size_t *plane) {
-  const EnsembleOutput &r = op->ens_out;
-  if (r.state != EnsembleOutput::LANDED)
-    return fail(RDYHIP_ERR_USER, r.state == EnsembleOutput::NONE ? "no ensemble state read has been begun (rdyhip_ens_state_read_begin)"
-                                                                 : "the ensemble state read has not been waited for (rdyhip_ens_state_read_wait)");
-  if (!(r.comps & comp))
-    return fail(RDYHIP_ERR_USER, "component 0x%x was not asked for by the last rdyhip_ens_state_read_begin (0x%x)", (unsigned)comp, (unsigned)r.comps);
-  *plane = (size_t)member * (size_t)popcount3(r.comps) + (size_t)popcount3(r.comps & (comp - 1));
-  return 0;
-}
-
-// the shared area table (and the workgroup count that goes with n_owned), this feature's records and pinned results
-int eout_sums_reserve(RDyHipOperator op) {
-  int rc = sums_reserve(op);
-  if (rc) return rc;
-  EnsembleOutput &r = op->ens_out;
-  const size_t    B = (size_t)op->ensemble.members;
-  if (!r.sums_done) HIP_TRY(hipEventCreateWithFlags(&r.sums_done, hipEventDisableTiming));
-  if (!r.h_sums) HIP_TRY(hipHostMalloc((void **)&r.h_sums, sizeof(double) * B * ERR_VALUES, hipHostMallocDefault));
-  if (!r.d_records.p) {
-    DevBuf<double> records;
-    rc = records.alloc(B * (size_t)(op->readout.err_wg + 1) * ERR_VALUES);
-    if (rc) return rc;
-    r.d_records = std::move(records);
-  }
   return 0;
 }
 
 // null operator, ensemble not enabled, unknown bits, not exactly one variable: the argument errors the five mean calls share
 int eout_means_check(RDyHipOperator op, int32_t vars, bool single) {
   int rc = ensemble_check(op);
-  if (rc) return rc;
-  if (vars & ~OUT_VARS) return fail(RDYHIP_ERR_USER, "unknown output variable bits 0x%x", (unsigned)(vars & ~OUT_VARS));
-  if (single && vars != RDYHIP_OUTPUT_SOLUTION && vars != RDYHIP_OUTPUT_PRIMITIVE_VARIABLES && vars != RDYHIP_OUTPUT_SOURCES)
-    return fail(RDYHIP_ERR_USER, "exactly one output variable is needed (got 0x%x)", (unsigned)vars);
-  return 0;
-}
-int eout_means_check_enabled(RDyHipOperator op, int32_t vars) {
-  for (int i = 0; i < 3; ++i)
-    if ((vars >> i & 1) && !op->ens_out.acc[i].p)
-      return fail(RDYHIP_ERR_USER, "ensemble output variable 0x%x is not enabled (rdyhip_ens_output_mean_enable)", 1u << i);
-  return 0;
+  return rc ? rc : means_check_vars(vars, single);
 }
 
 int eout_series_check(RDyHipOperator op) {
   int rc = ensemble_check(op);
-  if (rc) return rc;
-  if (!op->ens_out.series_enabled) return fail(RDYHIP_ERR_USER, "the ensemble observation series is not enabled (rdyhip_ens_series_enable)");
-  return 0;
+  return rc ? rc : series_check_enabled(op->ens_out.series, ENS_WORDS);
 }
 
 }  // namespace
@@ -116,127 +54,66 @@ extern "C" int rdyhip_ens_state_planes(RDyHipOperator op, int32_t comps, const d
 extern "C" int rdyhip_ens_state_read_begin(RDyHipOperator op, int32_t comps, const double *u_local, void *stream) {
   int rc = eout_check_comps(op, comps);
   if (rc) return rc;
-  EnsembleOutput &r = op->ens_out;
-  if (op->n_owned == 0) {   // nothing is launched or copied: the read has landed as soon as it is waited for
-    r.comps = comps;
-    r.state = EnsembleOutput::IN_FLIGHT;
-    return 0;
-  }
-  if (!u_local) return fail(RDYHIP_ERR_USER, "null u_local");
   hipStream_t st = (hipStream_t)stream;
-  const int   k  = popcount3(comps);
-  rc = eout_read_reserve(op, k);
-  if (rc) return rc;
-  // an earlier read that has not landed is given up; its copy may still be reading the device planes, so this launch waits for it
-  if (r.state == EnsembleOutput::IN_FLIGHT) HIP_TRY(hipStreamWaitEvent(st, r.done, 0));
-  r.state = EnsembleOutput::NONE;
-  rc = launch_ens_planes(op, comps, u_local, r.d_planes.p, st);
-  if (rc) return rc;
-  HIP_TRY(hipEventRecord(r.launched, st));
-  HIP_TRY(hipStreamWaitEvent(op->stage.copy, r.launched, 0));
-  HIP_TRY(hipMemcpyAsync(r.h_planes, r.d_planes.p, sizeof(double) * (size_t)op->ensemble.members * (size_t)k * (size_t)op->n_owned, hipMemcpyDeviceToHost,
-                         op->stage.copy));
-  HIP_TRY(hipEventRecord(r.done, op->stage.copy));
-  r.comps = comps;
-  r.state = EnsembleOutput::IN_FLIGHT;
-  return 0;
+  return read_begin(op, op->ens_out.planes, comps, (size_t)op->ensemble.members * (size_t)popcount(comps) * (size_t)op->n_owned, u_local, st,
+                    [&](double *planes) { return launch_ens_planes(op, comps, u_local, planes, st); });
 }
 
 extern "C" int rdyhip_ens_state_read_ready(RDyHipOperator op, int32_t *ready) {
   int rc = ensemble_check(op);
   if (rc) return rc;
   if (!ready) return fail(RDYHIP_ERR_USER, "null argument");
-  const EnsembleOutput &r = op->ens_out;
-  if (r.state == EnsembleOutput::NONE) return fail(RDYHIP_ERR_USER, "no ensemble state read has been begun (rdyhip_ens_state_read_begin)");
-  *ready = 1;
-  if (r.state == EnsembleOutput::IN_FLIGHT && op->n_owned > 0) {
-    const hipError_t e = hipEventQuery(r.done);
-    if (e == hipErrorNotReady) {
-      (void)hipGetLastError();
-      *ready = 0;
-    } else {
-      HIP_TRY(e);
-    }
-  }
-  return 0;
+  return read_ready(op, op->ens_out.planes, ENS_WORDS, ready);
 }
 
 extern "C" int rdyhip_ens_state_read_wait(RDyHipOperator op) {
   int rc = ensemble_check(op);
   if (rc) return rc;
-  EnsembleOutput &r = op->ens_out;
-  if (r.state == EnsembleOutput::NONE) return fail(RDYHIP_ERR_USER, "no ensemble state read has been begun (rdyhip_ens_state_read_begin)");
-  if (r.state == EnsembleOutput::IN_FLIGHT && op->n_owned > 0) HIP_TRY(hipEventSynchronize(r.done));
-  r.state = EnsembleOutput::LANDED;
-  return 0;
+  return read_wait(op, op->ens_out.planes, ENS_WORDS);
 }
 
 extern "C" int rdyhip_ens_state_read_get(RDyHipOperator op, int32_t member, int32_t comp, int32_t size, double *values) {
   int rc = eout_check_member_comp(op, member, comp);
   if (rc) return rc;
-  // CheckNumOwnedCells (src/rdydata.c:54-58)
-  if (size != op->n_owned) return fail(RDYHIP_ERR_ARG_SIZ, "The size of array (%d) is not equal to the number of owned cells (%d)", size, op->n_owned);
-  if (size > 0 && !values) return fail(RDYHIP_ERR_USER, "null values");
-  size_t plane = 0;
-  rc = eout_check_landed(op, member, comp, &plane);
-  if (rc) return rc;
-  if (size > 0) memcpy(values, op->ens_out.h_planes + plane * (size_t)op->n_owned, sizeof(double) * (size_t)size);
-  return 0;
+  return read_get(op, op->ens_out.planes, ENS_WORDS, member, comp, size, values);
 }
 
 extern "C" int rdyhip_ens_state_read_ptr(RDyHipOperator op, int32_t member, int32_t comp, const double **pinned_values) {
   int rc = eout_check_member_comp(op, member, comp);
   if (rc) return rc;
   if (!pinned_values) return fail(RDYHIP_ERR_USER, "null argument");
-  size_t plane = 0;
-  rc = eout_check_landed(op, member, comp, &plane);
-  if (rc) return rc;
-  *pinned_values = op->n_owned > 0 ? op->ens_out.h_planes + plane * (size_t)op->n_owned : nullptr;
-  return 0;
+  return read_landed_plane(op, op->ens_out.planes, ENS_WORDS, member, comp, pinned_values);
 }
 
 extern "C" int rdyhip_ens_error_sums(RDyHipOperator op, const double *u_local, const double *d_exact, void *stream) {
   int rc = ensemble_check(op);
   if (rc) return rc;
-  EnsembleOutput &r = op->ens_out;
-  if (op->n_owned == 0) {   // all zeros, nothing launched
-    r.sums_state = EnsembleOutput::IN_FLIGHT;
-    return 0;
-  }
-  if (!u_local) return fail(RDYHIP_ERR_USER, "null u_local");
-  rc = eout_sums_reserve(op);
-  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  // the records and the pinned results are shared by all calls: this one is ordered behind an earlier one that is still running
-  if (r.sums_state == EnsembleOutput::IN_FLIGHT) HIP_TRY(hipStreamWaitEvent(st, r.sums_done, 0));
-  const int    wg = op->readout.err_wg, B = op->ensemble.members;
-  double      *results = r.d_records.p + (size_t)B * (size_t)wg * ERR_VALUES;
-  hipLaunchKernelGGL(ens_error_partial_kernel, dim3(wg, B), dim3(ERR_BLOCK), 0, st, op->n_owned, eout_o2l(op), 3 * (int64_t)op->n_cells, u_local, d_exact,
-                     (const double *)op->readout.d_area.p, r.d_records.p);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(ens_error_finalize_kernel, dim3(B), dim3(ERR_BLOCK), 0, st, wg, (const double *)r.d_records.p, results);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(r.h_sums, results, sizeof(double) * (size_t)B * ERR_VALUES, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipEventRecord(r.sums_done, st));
-  r.sums_state = EnsembleOutput::IN_FLIGHT;
-  return 0;
+  const int   B  = op->ensemble.members;
+  // every member's workgroup records, then the B results: [B][err_wg + 1][10] as records of B x 10
+  return sums_begin(op, op->ens_out.sums, (size_t)B * ERR_VALUES, u_local, st, [&](int wg, double *records, double *results) {
+    hipLaunchKernelGGL(ens_error_partial_kernel, dim3(wg, B), dim3(ERR_BLOCK), 0, st, op->n_owned, owned_to_local(op), 3 * (int64_t)op->n_cells, u_local,
+                       d_exact, (const double *)op->readout.d_area.p, records);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ens_error_finalize_kernel, dim3(B), dim3(ERR_BLOCK), 0, st, wg, (const double *)records, results);
+    HIP_TRY(hipGetLastError());
+    return 0;
+  });
 }
 
 extern "C" int rdyhip_ens_error_sums_get(RDyHipOperator op, RDyHipErrorSums *out) {
   int rc = ensemble_check(op);
   if (rc) return rc;
   if (!out) return fail(RDYHIP_ERR_USER, "null argument");
-  EnsembleOutput &r = op->ens_out;
-  if (r.sums_state == EnsembleOutput::NONE) return fail(RDYHIP_ERR_USER, "no ensemble error sums have been asked for (rdyhip_ens_error_sums)");
+  rc = sums_wait(op, op->ens_out.sums, ENS_WORDS);
+  if (rc) return rc;
   static_assert(sizeof(RDyHipErrorSums) == sizeof(double) * ERR_VALUES, "RDyHipErrorSums is the ten doubles of a record");
   const size_t B = (size_t)op->ensemble.members;
   if (op->n_owned == 0) {
     memset(out, 0, sizeof(*out) * B);
   } else {
-    if (r.sums_state == EnsembleOutput::IN_FLIGHT) HIP_TRY(hipEventSynchronize(r.sums_done));
-    memcpy(out, r.h_sums, sizeof(*out) * B);
+    memcpy(out, op->ens_out.sums.h_sums, sizeof(*out) * B);
   }
-  r.sums_state = EnsembleOutput::LANDED;
   return 0;
 }
 
@@ -244,28 +121,20 @@ extern "C" int rdyhip_ens_output_mean_enable(RDyHipOperator op, int32_t vars) {
   int rc = eout_means_check(op, vars, false);
   if (rc) return rc;
   const size_t B = (size_t)op->ensemble.members;
-  for (int i = 0; i < 3; ++i) {
-    if (!(vars >> i & 1) || op->ens_out.acc[i].p) continue;   // an existing accumulator keeps its content
-    DevBuf<double> a;
-    rc = a.zeros(B * 3 * (size_t)op->n_owned);
-    if (rc) return rc;
-    op->ens_out.acc[i] = std::move(a);
-    op->ens_out.time[i].assign(B, 0.0);
-  }
-  return 0;
+  return means_enable(op->ens_out.means, vars, B * 3 * (size_t)op->n_owned, B);
 }
 
 extern "C" int rdyhip_ens_output_mean_accumulate(RDyHipOperator op, int32_t vars, const double *dts, const double *u_solution, const double *u_primitive,
                                                  void *stream) {
   int rc = eout_means_check(op, vars, false);
-  if (!rc) rc = eout_means_check_enabled(op, vars);
+  if (!rc) rc = means_check_enabled(op->ens_out.means, ENS_WORDS, vars);
   if (rc) return rc;
   if (!dts) return fail(RDYHIP_ERR_USER, "null dts");
   const bool sol = vars & RDYHIP_OUTPUT_SOLUTION, prim = vars & RDYHIP_OUTPUT_PRIMITIVE_VARIABLES, src = vars & RDYHIP_OUTPUT_SOURCES;
   if (sol && op->n_owned > 0 && !u_solution) return fail(RDYHIP_ERR_USER, "null u_solution (needed with RDYHIP_OUTPUT_SOLUTION)");
   if (prim && op->n_owned > 0 && !u_primitive) return fail(RDYHIP_ERR_USER, "null u_primitive (needed with RDYHIP_OUTPUT_PRIMITIVE_VARIABLES)");
-  EnsembleOutput &t = op->ens_out;
-  const int       B = op->ensemble.members;
+  OutputMeans &t = op->ens_out.means;
+  const int    B = op->ensemble.members;
   if (op->n_owned > 0 && vars) {
     EnsPerMember d{};
     for (int m = 0; m < B; ++m) d.v[m] = dts[m];
@@ -273,7 +142,7 @@ extern "C" int rdyhip_ens_output_mean_accumulate(RDyHipOperator op, int32_t vars
     const double *us = sol ? u_solution : nullptr, *up = prim ? u_primitive : nullptr, *ext = src ? op->ensemble.extsrc.p : nullptr;
     double       *acc_s = sol ? t.acc[0].p : nullptr, *acc_p = prim ? t.acc[1].p : nullptr, *acc_x = src ? t.acc[2].p : nullptr;
     const double  tiny_h = op->config.tiny_h, ha2 = op->config.h_anuga_regular * op->config.h_anuga_regular;
-    hipLaunchKernelGGL(ens_output_accumulate_kernel, eout_grid(op, op->n_owned), dim3(ENS_OUT_BLOCK), 0, (hipStream_t)stream, op->n_owned, eout_o2l(op), d,
+    hipLaunchKernelGGL(ens_output_accumulate_kernel, eout_grid(op, op->n_owned), dim3(ENS_OUT_BLOCK), 0, (hipStream_t)stream, op->n_owned, owned_to_local(op), d,
                        3 * (int64_t)op->n_cells, us, acc_s, up, tiny_h, ha2, acc_p, ext, acc_x);
     HIP_TRY(hipGetLastError());
   }
@@ -285,10 +154,10 @@ extern "C" int rdyhip_ens_output_mean_accumulate(RDyHipOperator op, int32_t vars
 
 extern "C" int rdyhip_ens_output_mean_get(RDyHipOperator op, int32_t var, double *d_mean, double *accumulated_times, void *stream) {
   int rc = eout_means_check(op, var, true);
-  if (!rc) rc = eout_means_check_enabled(op, var);
+  if (!rc) rc = means_check_enabled(op->ens_out.means, ENS_WORDS, var);
   if (rc) return rc;
-  const int       i = output_index(var), B = op->ensemble.members;
-  EnsembleOutput &t = op->ens_out;
+  const int          i = output_index(var), B = op->ensemble.members;
+  const OutputMeans &t = op->ens_out.means;
   if (op->n_owned > 0 && !d_mean) return fail(RDYHIP_ERR_USER, "null d_mean");
   // ComputeMean's PetscCheck (src/xdmf_output.c:213), for every member before anything is launched or written
   for (int m = 0; m < B; ++m)
@@ -308,69 +177,40 @@ extern "C" int rdyhip_ens_output_mean_get(RDyHipOperator op, int32_t var, double
 
 extern "C" int rdyhip_ens_output_mean_reset(RDyHipOperator op, int32_t vars, void *stream) {
   int rc = eout_means_check(op, vars, false);
-  if (!rc) rc = eout_means_check_enabled(op, vars);
+  if (!rc) rc = means_check_enabled(op->ens_out.means, ENS_WORDS, vars);
   if (rc) return rc;
-  EnsembleOutput &t = op->ens_out;
-  for (int i = 0; i < 3; ++i) {
-    if (!(vars >> i & 1)) continue;
-    if (op->n_owned > 0) HIP_TRY(hipMemsetAsync(t.acc[i].p, 0, t.acc[i].bytes(), (hipStream_t)stream));
-    std::fill(t.time[i].begin(), t.time[i].end(), 0.0);
-  }
-  return 0;
+  return means_reset(op, op->ens_out.means, vars, (hipStream_t)stream);
 }
 
 extern "C" int rdyhip_ens_output_mean_time(RDyHipOperator op, int32_t var, double *accumulated_times) {
   int rc = eout_means_check(op, var, true);
   if (rc) return rc;
   if (!accumulated_times) return fail(RDYHIP_ERR_USER, "null accumulated_times");
-  rc = eout_means_check_enabled(op, var);
-  if (rc) return rc;
-  const std::vector<double> &t = op->ens_out.time[output_index(var)];
-  std::copy(t.begin(), t.end(), accumulated_times);
-  return 0;
+  return means_time(op->ens_out.means, ENS_WORDS, var, accumulated_times);
 }
 
 extern "C" int rdyhip_ens_series_enable(RDyHipOperator op, int32_t num_sites, const int32_t *owned_cell_ids, int32_t capacity) {
   int rc = ensemble_check(op);
   if (rc) return rc;
-  if (num_sites < 0 || capacity < 0) return fail(RDYHIP_ERR_USER, "negative number of sites (%d) or capacity (%d)", num_sites, capacity);
-  if (num_sites > 0 && !owned_cell_ids) return fail(RDYHIP_ERR_USER, "null owned_cell_ids");
-  EnsembleOutput &t = op->ens_out;
-  if (t.series_enabled) return fail(RDYHIP_ERR_USER, "the ensemble observation series is enabled already");
-  for (int32_t i = 0; i < num_sites; ++i)
-    if (owned_cell_ids[i] < 0 || owned_cell_ids[i] >= op->n_owned)
-      return fail(RDYHIP_ERR_USER, "observation site %d: owned cell %d out of range [0, %d)", i, owned_cell_ids[i], op->n_owned);
-  std::vector<int32_t> local(owned_cell_ids, owned_cell_ids + num_sites);
-  if (!op->prefix && num_sites > 0) {   // owned -> local through the operator's own table
-    std::vector<int32_t> o2l((size_t)op->n_owned);
-    HIP_TRY(hipMemcpy(o2l.data(), op->d_o2l.p, sizeof(int32_t) * (size_t)op->n_owned, hipMemcpyDeviceToHost));
-    for (auto &c : local) c = o2l[(size_t)c];
-  }
-  const size_t    B = (size_t)op->ensemble.members;
-  DevBuf<int32_t> sites;
-  DevBuf<double>  log;
-  rc = sites.upload(local);
-  if (!rc) rc = log.zeros((size_t)capacity * B * (size_t)num_sites * 3);
+  std::vector<int32_t> local;
+  rc = series_sites(op, op->ens_out.series, ENS_WORDS, num_sites, owned_cell_ids, capacity, local);
   if (rc) return rc;
-  t.d_sites  = std::move(sites);
-  t.d_log    = std::move(log);
-  t.entries  = num_sites;
-  t.capacity = capacity;
-  t.records  = 0;
-  t.times.clear();
-  t.times.reserve((size_t)capacity * B);
-  t.series_enabled = true;
-  return 0;
+  const size_t B = (size_t)op->ensemble.members;
+  SeriesLog    s;
+  rc = s.d_sites.upload(local);
+  if (!rc) rc = series_alloc_log(&s, num_sites, capacity, B * 3, B);
+  if (!rc) op->ens_out.series = std::move(s);
+  return rc;
 }
 
 extern "C" int rdyhip_ens_series_record(RDyHipOperator op, const double *times, const double *u_local, void *stream) {
   int rc = eout_series_check(op);
   if (rc) return rc;
-  EnsembleOutput &t = op->ens_out;
+  SeriesLog &t = op->ens_out.series;
   if (!times) return fail(RDYHIP_ERR_USER, "null times");
   if (t.entries > 0 && !u_local) return fail(RDYHIP_ERR_USER, "null u_local");
-  if (t.records >= t.capacity)
-    return fail(RDYHIP_ERR_USER, "ensemble series: the log is full (%d records); read it and call rdyhip_ens_series_clear", t.capacity);
+  rc = series_check_room(t, ENS_WORDS);
+  if (rc) return rc;
   const int B = op->ensemble.members;
   if (t.entries > 0) {
     hipLaunchKernelGGL(ens_series_observe_kernel, eout_grid(op, t.entries), dim3(ENS_OUT_BLOCK), 0, (hipStream_t)stream, t.entries, B,
@@ -385,34 +225,22 @@ extern "C" int rdyhip_ens_series_record(RDyHipOperator op, const double *times, 
 extern "C" int rdyhip_ens_series_info(RDyHipOperator op, int32_t *entries, int32_t *count, int32_t *capacity) {
   int rc = eout_series_check(op);
   if (rc) return rc;
-  const EnsembleOutput &t = op->ens_out;
-  if (entries) *entries = t.entries;
-  if (count) *count = t.records;
-  if (capacity) *capacity = t.capacity;
+  series_info(op->ens_out.series, entries, count, capacity);
   return 0;
 }
 
 extern "C" int rdyhip_ens_series_read(RDyHipOperator op, int32_t first, int32_t count, double *times, double *values, void *stream) {
   int rc = eout_series_check(op);
   if (rc) return rc;
-  const EnsembleOutput &t = op->ens_out;
-  if (first < 0 || count < 0 || (int64_t)first + count > (int64_t)t.records)
-    return fail(RDYHIP_ERR_USER, "ensemble series: records [%d, %d + %d) are not in the log (%d records)", first, first, count, t.records);
-  const size_t B = (size_t)op->ensemble.members, row = B * (size_t)t.entries * 3;
-  if (count > 0 && (!times || (row > 0 && !values))) return fail(RDYHIP_ERR_USER, "null times / values");
-  if (count == 0) return 0;
-  std::copy(t.times.begin() + (size_t)first * B, t.times.begin() + ((size_t)first + (size_t)count) * B, times);
-  if (row > 0)
-    HIP_TRY(hipMemcpyAsync(values, t.d_log.p + (size_t)first * row, sizeof(double) * (size_t)count * row, hipMemcpyDeviceToHost, (hipStream_t)stream));
-  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-  return 0;
+  const SeriesLog &t = op->ens_out.series;
+  const size_t     B = (size_t)op->ensemble.members;
+  return series_read(t, "ensemble series", B * (size_t)t.entries * 3, B, first, count, times, values, (hipStream_t)stream);
 }
 
 extern "C" int rdyhip_ens_series_clear(RDyHipOperator op) {
   int rc = eout_series_check(op);
   if (rc) return rc;
-  op->ens_out.times.clear();
-  op->ens_out.records = 0;
+  series_clear(op->ens_out.series);
   return 0;
 }
 
@@ -423,7 +251,7 @@ extern "C" int rdyhip_ens_stats(RDyHipOperator op, int32_t comps, const double *
   if (!u_local || !d_stats) return fail(RDYHIP_ERR_USER, "null u_local / d_stats");
   const int B = op->ensemble.members;
   hipLaunchKernelGGL(ens_stats_kernel, dim3((unsigned)((op->n_owned + ENS_OUT_BLOCK - 1) / ENS_OUT_BLOCK)), dim3(ENS_OUT_BLOCK), 0, (hipStream_t)stream,
-                     op->n_owned, eout_o2l(op), (int)comps, B, 1.0 / (double)B, 3 * (int64_t)op->n_cells, u_local, d_stats);
+                     op->n_owned, owned_to_local(op), (int)comps, B, 1.0 / (double)B, 3 * (int64_t)op->n_cells, u_local, d_stats);
   HIP_TRY(hipGetLastError());
   return 0;
 }

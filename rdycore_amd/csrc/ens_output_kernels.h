@@ -113,7 +113,7 @@ __global__ void __launch_bounds__(ERR_BLOCK) ens_error_partial_kernel(int n_owne
     }
     v[9] += a;
   }
-  err_block_fold_store(v, records + (m * gridDim.x + blockIdx.x) * ERR_VALUES);
+  err_block_fold_store<3>(v, records + (m * gridDim.x + blockIdx.x) * ERR_VALUES);
 }
 
 // results[blockIdx.x][ERR_VALUES] = the fold of records[blockIdx.x][0 .. n_records); workgroup m for member m
@@ -124,9 +124,9 @@ __global__ void __launch_bounds__(ERR_BLOCK) ens_error_finalize_kernel(int n_rec
   for (int i = 0; i < ERR_VALUES; ++i) v[i] = 0.0;
   for (int r = threadIdx.x; r < n_records; r += ERR_BLOCK) {
 #pragma unroll
-    for (int i = 0; i < ERR_VALUES; ++i) v[i] = err_fold(i, v[i], rm[(int64_t)r * ERR_VALUES + i]);
+    for (int i = 0; i < ERR_VALUES; ++i) v[i] = err_fold<3>(i, v[i], rm[(int64_t)r * ERR_VALUES + i]);
   }
-  err_block_fold_store(v, results + (int64_t)blockIdx.x * ERR_VALUES);
+  err_block_fold_store<3>(v, results + (int64_t)blockIdx.x * ERR_VALUES);
 }
 
 // blockIdx.y: the member.  Accumulators and ext are [B][n_owned][3]; a null pointer leaves its variable out.

@@ -102,35 +102,74 @@ struct StageRing {
   }
 };
 
-// The read-out of the state (rdyhip_state_read_*, rdyhip_error_sums; readout_kernels.h): device planes and pinned host planes
-// of the getters, the areas / partial records / pinned result of the error sums, and the events the host waits on.  Everything
-// is allocated by the first call that needs it and grows only.
-struct Readout {
+// The pieces the output of a state is made of -- the SWE state, the [cell][3 + NT] tracer state and the [B][cell][3] ensemble state
+// each hold instances of their own, so that a read of one never disturbs a read of another.  Everything is allocated by the first
+// call that needs it and grows only; a piece that owns pinned memory waits for a copy that still writes it before it frees it.
+
+// One read of planes of a state through pinned memory (rdyhip_*state_read_*; output_shared.h)
+struct PlaneRead {
   enum State { NONE, IN_FLIGHT, LANDED };
-  // the getters
-  DevBuf<double> d_planes;            // [popcount(comps)][n_owned], room for the widest mask asked for so far
+  DevBuf<double> d_planes;            // ([B])[popcount(comps)][n_owned], room for the widest mask asked for so far
   double        *h_planes = nullptr;  // pinned, as many doubles as d_planes
   size_t         h_cap = 0;
   hipEvent_t     launched = nullptr, done = nullptr;   // the de-interleave launch on the caller's stream; the copy on StageRing::copy
   State          state = NONE;
   int32_t        comps = 0;           // the mask of the last begin
-  // the error sums
-  DevBuf<double> d_area, d_records;   // [n_owned]; [err_wg + 1][10]: the workgroups' records, then the result
-  double        *h_sums = nullptr;    // pinned, 10 doubles (RDyHipErrorSums)
-  hipEvent_t     sums_done = nullptr;
-  State          sums_state = NONE;
-  int            err_wg = 0;
-  Readout() = default;
-  Readout(const Readout &) = delete;
-  Readout &operator=(const Readout &) = delete;
-  ~Readout() {
+  PlaneRead() = default;
+  PlaneRead(const PlaneRead &) = delete;
+  PlaneRead &operator=(const PlaneRead &) = delete;
+  ~PlaneRead() {
+    if (state == IN_FLIGHT && done) (void)hipEventSynchronize(done);   // the copy writes h_planes
     if (h_planes) (void)hipHostFree(h_planes);
-    if (h_sums) (void)hipHostFree(h_sums);
     if (launched) (void)hipEventDestroy(launched);
     if (done) (void)hipEventDestroy(done);
-    if (sums_done) (void)hipEventDestroy(sums_done);
   }
-  size_t bytes() const { return d_planes.bytes() + d_area.bytes() + d_records.bytes(); }
+};
+
+// The error sums of a state (rdyhip_*error_sums; output_shared.h): records of `width` doubles (SWE: 10, tracers: 3 N + 1,
+// ensemble: B x 10)
+struct SumsRead {
+  DevBuf<double>   d_records;         // [err_wg + 1][width]: the workgroups' records, then the result
+  double          *h_sums = nullptr;  // pinned, `width` doubles
+  hipEvent_t       done = nullptr;
+  PlaneRead::State state = PlaneRead::NONE;
+  SumsRead() = default;
+  SumsRead(const SumsRead &) = delete;
+  SumsRead &operator=(const SumsRead &) = delete;
+  ~SumsRead() {
+    if (state == PlaneRead::IN_FLIGHT && done) (void)hipEventSynchronize(done);   // the copy writes h_sums
+    if (h_sums) (void)hipHostFree(h_sums);
+    if (done) (void)hipEventDestroy(done);
+  }
+};
+
+// rdyhip_*output_mean_*: one accumulator per enabled variable (bit i of RDYHIP_OUTPUT_*), [n_owned][3] for the SWE state,
+// [n_owned][N] for tracers, [B][n_owned][3] for an ensemble, and the time it spans: one per member (one where there are none)
+struct OutputMeans {
+  DevBuf<double>      acc[3];
+  std::vector<double> time[3];
+  size_t bytes() const { return acc[0].bytes() + acc[1].bytes() + acc[2].bytes(); }
+};
+
+// One device log of WriteTimeSeries: `capacity` records of `entries` rows each, and the time(s) of every record on the host
+// (an ensemble: B per record)
+struct SeriesLog {
+  bool                enabled = false;
+  int32_t             entries = 0, capacity = 0, records = 0;
+  DevBuf<double>      d_log;
+  DevBuf<int32_t>     d_sites;          // observations: [entries] local cell of every site
+  std::vector<double> times;
+  size_t bytes() const { return d_log.bytes() + d_sites.bytes(); }
+};
+
+// The read-out of the SWE state (rdyhip_state_read_*, rdyhip_error_sums; readout_kernels.h).  The area table and the workgroup
+// count of the error sums serve the tracer and ensemble sums too.
+struct Readout {
+  PlaneRead      planes;
+  SumsRead       sums;
+  DevBuf<double> d_area;   // [n_owned]
+  int            err_wg = 0;
+  size_t bytes() const { return planes.d_planes.bytes() + d_area.bytes() + sums.d_records.bytes(); }
 };
 
 // One non-blocking read of the Courant record(s) (rdyhip_diagnostics_begin / _ready / _wait; diagnostics_calls.h), one per
@@ -162,26 +201,13 @@ struct Rk4Workspace {
   size_t bytes() const { return y.bytes() + k[0].bytes() + k[1].bytes() + k[2].bytes() + k[3].bytes(); }
 };
 
-// rdyhip_output_mean_*: one [n_owned][3] accumulator per enabled variable (bit i of RDYHIP_OUTPUT_*) and the time it spans
-struct OutputMeans {
-  DevBuf<double> acc[3];
-  double         time[3] = {0.0, 0.0, 0.0};
-  size_t bytes() const { return acc[0].bytes() + acc[1].bytes() + acc[2].bytes(); }
-};
-
-// rdyhip_series_*: one device log of WriteTimeSeries, `capacity` records of entries x 3 doubles each, and the time of every
-// record on the host
-struct Series {
-  bool                 enabled = false;
-  int32_t              entries = 0, capacity = 0;
-  DevBuf<double>       d_log;
-  std::vector<double>  times;            // size() = the number of records
-  DevBuf<int32_t>      d_sites;          // observations: [entries] local cell of every site
+// rdyhip_series_*: the log of the observations or of the boundary fluxes, records of entries x 3 doubles
+struct Series : SeriesLog {
   DevBuf<int32_t>      d_slot;           // boundary fluxes: [K] row of boundary edge k in a record, or -1
   DevBuf<double>       d_len;            //                  [K] edge lengths
   double               btime = 0.0;      //                  boundary_fluxes.accumulated_time
   std::vector<int32_t> h_edge, h_bnd;    //                  [entries] local edge id and boundary of every recorded edge
-  size_t bytes() const { return d_log.bytes() + d_sites.bytes() + d_slot.bytes() + d_len.bytes(); }
+  size_t bytes() const { return SeriesLog::bytes() + d_slot.bytes() + d_len.bytes(); }
 };
 
 // rdyhip_tracers_* (tracer_kernels.h): N = 3 + n values per row.  Boundary values and fluxes [K][N] and the tracer sources
@@ -195,49 +221,19 @@ struct TracerState {
   size_t bytes() const { return bvalues.bytes() + bflux.bytes() + src.bytes() + pv.bytes(); }
 };
 
-// rdyhip_tracer_state_* / _error_sums / _output_mean_* / _series_* (tracer_output_kernels.h): the read-out, the error sums, the
-// output means and the observation series of the [cell][N = 3 + NT] state, each a copy of what Readout, OutputMeans and Series
-// hold for rows of three -- of their own, so that a flow read and a tracer read may be in flight together.  The area table of
-// the error sums is Readout::d_area.  Everything is allocated by the first call that needs it (means, series: by their enable).
-struct TracerOutput {
-  enum State { NONE, IN_FLIGHT, LANDED };
-  // the getters
-  DevBuf<double> d_planes;            // [popcount(comps)][n_owned], room for the widest mask asked for so far
-  double        *h_planes = nullptr;  // pinned, as many doubles as d_planes
-  size_t         h_cap = 0;
-  hipEvent_t     launched = nullptr, done = nullptr;
-  State          state = NONE;
-  int32_t        comps = 0;           // the mask of the last begin
-  // the error sums
-  DevBuf<double> d_records;           // [err_wg + 1][3 N + 1]: the workgroups' records, then the result
-  double        *h_sums = nullptr;    // pinned, 3 N + 1 doubles
-  hipEvent_t     sums_done = nullptr;
-  State          sums_state = NONE;
-  // the output means: one [n_owned][N] accumulator per enabled variable and the time it spans
-  DevBuf<double> acc[3];
-  double         time[3] = {0.0, 0.0, 0.0};
-  // the observation series: `capacity` records of entries x N doubles, the time of every record on the host
-  bool                series_enabled = false;
-  int32_t             entries = 0, capacity = 0;
-  DevBuf<double>      d_log;
-  DevBuf<int32_t>     d_sites;        // [entries] local cell of every site
-  std::vector<double> times;          // size() = the number of records
-  TracerOutput() = default;
-  TracerOutput(const TracerOutput &) = delete;
-  TracerOutput &operator=(const TracerOutput &) = delete;
-  ~TracerOutput() {
-    if (state == IN_FLIGHT && done) (void)hipEventSynchronize(done);   // the copies write pinned memory
-    if (sums_state == IN_FLIGHT && sums_done) (void)hipEventSynchronize(sums_done);
-    if (h_planes) (void)hipHostFree(h_planes);
-    if (h_sums) (void)hipHostFree(h_sums);
-    if (launched) (void)hipEventDestroy(launched);
-    if (done) (void)hipEventDestroy(done);
-    if (sums_done) (void)hipEventDestroy(sums_done);
-  }
-  size_t bytes() const {
-    return d_planes.bytes() + d_records.bytes() + acc[0].bytes() + acc[1].bytes() + acc[2].bytes() + d_log.bytes() + d_sites.bytes();
-  }
+// rdyhip_tracer_state_* / _error_sums / _output_mean_* / _series_* (tracer_output_kernels.h) and rdyhip_ens_state_* / ... / _stats
+// (ens_output_kernels.h): the read-out, the error sums, the output means and the observation series of the [cell][N = 3 + NT]
+// state and of the [B][cell][3] ensemble state.  The area table of the error sums is Readout::d_area.  Means and series are
+// allocated by their enable.
+struct StateOutput {
+  PlaneRead   planes;
+  SumsRead    sums;
+  OutputMeans means;
+  SeriesLog   series;
+  size_t bytes() const { return planes.d_planes.bytes() + sums.d_records.bytes() + means.bytes() + series.bytes(); }
 };
+using TracerOutput   = StateOutput;
+using EnsembleOutput = StateOutput;
 
 // rdyhip_ensemble_* (ensemble_kernels.h): B members on this operator's mesh, all allocated by rdyhip_ensemble_enable.  The
 // launch is (grid, groups) workgroups, every group walking per_group members (the last one maybe fewer).
@@ -251,51 +247,6 @@ struct EnsembleState {
   bool                       hr = false;  // enabled by rdyhip_ens_hr_enable: the evaluations run ensemble_hr_kernel
   size_t bytes() const {
     return mannings.bytes() + extsrc.bytes() + bvalues.bytes() + bflux.bytes() + blk_max.bytes() + blk_pos.bytes() + d_courant.bytes();
-  }
-};
-
-// rdyhip_ens_state_* / _error_sums / _output_mean_* / _series_* / _stats (ens_output_kernels.h): the read-out, the error sums, the
-// output means and the observation series of the [B][cell][3] ensemble state, each what Readout, OutputMeans and Series hold for
-// one state, B times over -- of their own, so that the SWE read-out of the same operator is never disturbed.  The area table of
-// the error sums is Readout::d_area.  Everything is allocated by the first call that needs it (means, series: by their enable).
-struct EnsembleOutput {
-  enum State { NONE, IN_FLIGHT, LANDED };
-  // the getters
-  DevBuf<double> d_planes;            // [B][popcount(comps)][n_owned], room for the widest mask asked for so far
-  double        *h_planes = nullptr;  // pinned, as many doubles as d_planes
-  size_t         h_cap = 0;
-  hipEvent_t     launched = nullptr, done = nullptr;
-  State          state = NONE;
-  int32_t        comps = 0;           // the mask of the last begin
-  // the error sums
-  DevBuf<double> d_records;           // [B][err_wg + 1][10]: every member's workgroup records, then the B results
-  double        *h_sums = nullptr;    // pinned, [B][10] (B x RDyHipErrorSums)
-  hipEvent_t     sums_done = nullptr;
-  State          sums_state = NONE;
-  // the output means: one [B][n_owned][3] accumulator per enabled variable and, per variable, the time every member's spans
-  DevBuf<double>      acc[3];
-  std::vector<double> time[3];        // [B] each
-  // the observation series: `capacity` records of B x entries x 3 doubles, the B times of every record on the host
-  bool                series_enabled = false;
-  int32_t             entries = 0, capacity = 0;
-  DevBuf<double>      d_log;
-  DevBuf<int32_t>     d_sites;        // [entries] local cell of every site
-  std::vector<double> times;          // [records][B]
-  int32_t             records = 0;
-  EnsembleOutput() = default;
-  EnsembleOutput(const EnsembleOutput &) = delete;
-  EnsembleOutput &operator=(const EnsembleOutput &) = delete;
-  ~EnsembleOutput() {
-    if (state == IN_FLIGHT && done) (void)hipEventSynchronize(done);   // the copies write pinned memory
-    if (sums_state == IN_FLIGHT && sums_done) (void)hipEventSynchronize(sums_done);
-    if (h_planes) (void)hipHostFree(h_planes);
-    if (h_sums) (void)hipHostFree(h_sums);
-    if (launched) (void)hipEventDestroy(launched);
-    if (done) (void)hipEventDestroy(done);
-    if (sums_done) (void)hipEventDestroy(sums_done);
-  }
-  size_t bytes() const {
-    return d_planes.bytes() + d_records.bytes() + acc[0].bytes() + acc[1].bytes() + acc[2].bytes() + d_log.bytes() + d_sites.bytes();
   }
 };
 
@@ -402,13 +353,16 @@ struct RDyHipOperator_s : LayoutCounts {
   }
 };
 
+// The owned-to-local table the kernels take: none where the owned cells are the first n_owned local cells in order
+static const int32_t *owned_to_local(const RDyHipOperator_s *op) { return op->prefix ? nullptr : op->d_o2l.p; }
+
 // What every launcher (gradients, RHS, tracers, ensembles) passes of the operator as it is; each sets only its own work,
 // fields and flags on top.  A new field of KernelArgs that all of them need goes here.
 static KernelArgs kernel_args_base(const RDyHipOperator_s *op) {
   KernelArgs a{};
   a.n_owned    = op->n_owned;
   a.stride     = op->stride;
-  a.o2l        = op->prefix ? nullptr : op->d_o2l.p;
+  a.o2l        = owned_to_local(op);
   a.cold       = op->d_cold.p;
   a.coef       = op->d_coef.p;
   a.dzdx       = op->d_dzdx.p;

@@ -70,6 +70,20 @@ auto with_flag(bool b, F f) {
   return b ? f(std::true_type()) : f(std::false_type());
 }
 
+// ... and std::integral_constant<int, NT> for an operator's number of tracers, 1..7 (checked by the enable calls)
+template <class F>
+auto with_tracer_count(int nt, F f) {
+  switch (nt) {
+    case 1: return f(std::integral_constant<int, 1>());
+    case 2: return f(std::integral_constant<int, 2>());
+    case 3: return f(std::integral_constant<int, 3>());
+    case 4: return f(std::integral_constant<int, 4>());
+    case 5: return f(std::integral_constant<int, 5>());
+    case 6: return f(std::integral_constant<int, 6>());
+    default: return f(std::integral_constant<int, 7>());
+  }
+}
+
 // The instantiation of the tiled kernel for (slots per cell, source method, f = rhs (else f += rhs), HR, the forward-Euler update
 // fused into the stores (rdyhip_euler_step; always f = rhs), F -- Euler step: u_out -- stored with the non-temporal hint,
 // normals from the operator's table (swe_rhs_ntab_kernel) instead of one streamed double per record)
@@ -822,6 +836,7 @@ int rdyhip_layout_info(RDyHipOperator op, RDyHipLayoutInfo *info) {
 #include "halo_exchange.h"
 #include "halo_plan.h"
 #include "rk_calls.h"
+#include "output_shared.h"
 #include "output_calls.h"
 #include "series_calls.h"
 #include "readout_calls.h"

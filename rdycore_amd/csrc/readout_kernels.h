@@ -60,29 +60,35 @@ __global__ void state_planes_kernel(int n_owned, const int32_t *__restrict__ o2l
   if (comps & 4) *p = v2;
 }
 
-// values 0..5 and 9 are sums, 6..8 maxima
-__device__ __forceinline__ double err_fold(int i, double a, double b) { return (i >= 6 && i < 9) ? fmax(a, b) : a + b; }
+// A record of 3 N + 1 values (N = 3: the SWE and ensemble records of ERR_VALUES; tracers: N = 3 + NT): values [2 N, 3 N) are
+// maxima, the others sums
+template <int N>
+__device__ __forceinline__ double err_fold(int i, double a, double b) {
+  return (i >= 2 * N && i < 3 * N) ? fmax(a, b) : a + b;
+}
 
-// The workgroup's fold of v[ERR_VALUES]: lanes of a wave by a shuffle tree, then the waves in order; thread 0 stores the record.
-__device__ __forceinline__ void err_block_fold_store(double (&v)[ERR_VALUES], double *__restrict__ record) {
-  __shared__ double waves[ERR_WAVES][ERR_VALUES];
+// The workgroup's fold of v[3 N + 1]: lanes of a wave by a shuffle tree, then the waves in order; thread 0 stores the record.
+template <int N>
+__device__ __forceinline__ void err_block_fold_store(double (&v)[3 * N + 1], double *__restrict__ record) {
+  constexpr int   V = 3 * N + 1;
+  __shared__ double waves[ERR_WAVES][V];
 #pragma unroll
-  for (int i = 0; i < ERR_VALUES; ++i) {
+  for (int i = 0; i < V; ++i) {
 #pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v[i] = err_fold(i, v[i], __shfl_down(v[i], d, 64));
+    for (int d = 32; d > 0; d >>= 1) v[i] = err_fold<N>(i, v[i], __shfl_down(v[i], d, 64));
   }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) {
 #pragma unroll
-    for (int i = 0; i < ERR_VALUES; ++i) waves[wave][i] = v[i];
+    for (int i = 0; i < V; ++i) waves[wave][i] = v[i];
   }
   __syncthreads();
   if (threadIdx.x == 0) {
 #pragma unroll
-    for (int i = 0; i < ERR_VALUES; ++i) {
+    for (int i = 0; i < V; ++i) {
       double r = waves[0][i];
 #pragma unroll
-      for (int w = 1; w < ERR_WAVES; ++w) r = err_fold(i, r, waves[w][i]);
+      for (int w = 1; w < ERR_WAVES; ++w) r = err_fold<N>(i, r, waves[w][i]);
       record[i] = r;
     }
   }
@@ -114,7 +120,7 @@ __global__ void __launch_bounds__(ERR_BLOCK) error_partial_kernel(int n_owned, c
     }
     v[9] += a;
   }
-  err_block_fold_store(v, records + (int64_t)blockIdx.x * ERR_VALUES);
+  err_block_fold_store<3>(v, records + (int64_t)blockIdx.x * ERR_VALUES);
 }
 
 // result[ERR_VALUES] = the fold of records[0 .. n_records); one workgroup
@@ -124,9 +130,9 @@ __global__ void __launch_bounds__(ERR_BLOCK) error_finalize_kernel(int n_records
   for (int i = 0; i < ERR_VALUES; ++i) v[i] = 0.0;
   for (int r = threadIdx.x; r < n_records; r += ERR_BLOCK) {
 #pragma unroll
-    for (int i = 0; i < ERR_VALUES; ++i) v[i] = err_fold(i, v[i], records[(int64_t)r * ERR_VALUES + i]);
+    for (int i = 0; i < ERR_VALUES; ++i) v[i] = err_fold<3>(i, v[i], records[(int64_t)r * ERR_VALUES + i]);
   }
-  err_block_fold_store(v, result);
+  err_block_fold_store<3>(v, result);
 }
 
 }  // namespace rdyhip

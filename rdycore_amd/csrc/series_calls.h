@@ -16,37 +16,17 @@ int series_check_enabled(const Series *s, int32_t kind) {
                                kind == RDYHIP_SERIES_OBSERVATIONS ? "observations" : "boundary_fluxes");
   return 0;
 }
-// the log of `capacity` records of `entries` rows
-int series_alloc_log(Series *s, int32_t entries, int32_t capacity) {
-  int rc = s->d_log.zeros((size_t)capacity * (size_t)entries * 3);
-  if (rc) return rc;
-  s->entries  = entries;
-  s->capacity = capacity;
-  s->times.clear();
-  s->times.reserve((size_t)capacity);
-  s->enabled = true;
-  return 0;
-}
 
 }  // namespace
 
 extern "C" int rdyhip_series_observations_enable(RDyHipOperator op, int32_t num_sites, const int32_t *owned_cell_ids, int32_t capacity) {
   if (!op) return fail(RDYHIP_ERR_USER, "null operator");
-  if (num_sites < 0 || capacity < 0) return fail(RDYHIP_ERR_USER, "negative number of sites (%d) or capacity (%d)", num_sites, capacity);
-  if (num_sites > 0 && !owned_cell_ids) return fail(RDYHIP_ERR_USER, "null owned_cell_ids");
-  if (op->series[0].enabled) return fail(RDYHIP_ERR_USER, "the observation series is enabled already");
-  for (int32_t i = 0; i < num_sites; ++i)
-    if (owned_cell_ids[i] < 0 || owned_cell_ids[i] >= op->n_owned)
-      return fail(RDYHIP_ERR_USER, "observation site %d: owned cell %d out of range [0, %d)", i, owned_cell_ids[i], op->n_owned);
-  std::vector<int32_t> local(owned_cell_ids, owned_cell_ids + num_sites);
-  if (!op->prefix && num_sites > 0) {   // owned -> local through the operator's own table
-    std::vector<int32_t> o2l((size_t)op->n_owned);
-    HIP_TRY(hipMemcpy(o2l.data(), op->d_o2l.p, sizeof(int32_t) * (size_t)op->n_owned, hipMemcpyDeviceToHost));
-    for (auto &c : local) c = o2l[(size_t)c];
-  }
+  std::vector<int32_t> local;
+  int rc = series_sites(op, op->series[0], SWE_WORDS, num_sites, owned_cell_ids, capacity, local);
+  if (rc) return rc;
   Series s;
-  int    rc = s.d_sites.upload(local);
-  if (!rc) rc = series_alloc_log(&s, num_sites, capacity);
+  rc = s.d_sites.upload(local);
+  if (!rc) rc = series_alloc_log(&s, num_sites, capacity, 3);
   if (!rc) op->series[0] = std::move(s);
   return rc;
 }
@@ -66,7 +46,7 @@ extern "C" int rdyhip_series_boundary_fluxes_enable(RDyHipOperator op, int32_t n
   Series s;
   rc = s.d_slot.upload(P.slot);
   if (!rc) rc = s.d_len.upload(op->h_blen);
-  if (!rc) rc = series_alloc_log(&s, P.E, capacity);
+  if (!rc) rc = series_alloc_log(&s, P.E, capacity, 3);
   if (rc) return rc;
   s.h_edge = std::move(P.edge);
   s.h_bnd  = std::move(P.boundary);
@@ -111,9 +91,9 @@ extern "C" int rdyhip_series_record(RDyHipOperator op, int32_t kind, double time
   if (rc) return rc;
   const bool obs = kind == RDYHIP_SERIES_OBSERVATIONS;
   if (obs && s->entries > 0 && !u_local) return fail(RDYHIP_ERR_USER, "null u_local (needed with RDYHIP_SERIES_OBSERVATIONS)");
-  if ((int64_t)s->times.size() >= (int64_t)s->capacity)
+  if (s->records >= s->capacity)
     return fail(RDYHIP_ERR_USER, "series %d: the log is full (%d records); read it and call rdyhip_series_clear", kind, s->capacity);
-  const int64_t r = (int64_t)s->times.size();
+  const int64_t r = s->records;
   if (s->entries > 0) {
     if (obs) {
       hipLaunchKernelGGL(series_observe_kernel, dim3((unsigned)((s->entries + SERIES_BLOCK - 1) / SERIES_BLOCK)), dim3(SERIES_BLOCK), 0, (hipStream_t)stream,
@@ -127,6 +107,7 @@ extern "C" int rdyhip_series_record(RDyHipOperator op, int32_t kind, double time
     HIP_TRY(hipGetLastError());
   }
   s->times.push_back(time);
+  ++s->records;
   if (!obs) s->btime = 0.0;   // ResetAccumulatedBoundaryFluxes
   return 0;
 }
@@ -136,9 +117,7 @@ extern "C" int rdyhip_series_info(RDyHipOperator op, int32_t kind, int32_t *entr
   int rc = series_check(op, kind, &s);
   if (!rc) rc = series_check_enabled(s, kind);
   if (rc) return rc;
-  if (entries) *entries = s->entries;
-  if (count) *count = (int32_t)s->times.size();
-  if (capacity) *capacity = s->capacity;
+  series_info(*s, entries, count, capacity);
   if (accumulated_time) *accumulated_time = s->btime;   // the observations' stays 0
   return 0;
 }
@@ -148,16 +127,8 @@ extern "C" int rdyhip_series_read(RDyHipOperator op, int32_t kind, int32_t first
   int rc = series_check(op, kind, &s);
   if (!rc) rc = series_check_enabled(s, kind);
   if (rc) return rc;
-  if (first < 0 || count < 0 || (int64_t)first + count > (int64_t)s->times.size())
-    return fail(RDYHIP_ERR_USER, "series %d: records [%d, %d + %d) are not in the log (%d records)", kind, first, first, count, (int)s->times.size());
-  const size_t row = (size_t)s->entries * 3;
-  if (count > 0 && (!times || (row > 0 && !values))) return fail(RDYHIP_ERR_USER, "null times / values");
-  if (count == 0) return 0;
-  std::copy(s->times.begin() + first, s->times.begin() + first + count, times);
-  if (row > 0)
-    HIP_TRY(hipMemcpyAsync(values, s->d_log.p + (size_t)first * row, sizeof(double) * (size_t)count * row, hipMemcpyDeviceToHost, (hipStream_t)stream));
-  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-  return 0;
+  const std::string name = "series " + std::to_string(kind);
+  return series_read(*s, name.c_str(), (size_t)s->entries * 3, 1, first, count, times, values, (hipStream_t)stream);
 }
 
 extern "C" int rdyhip_series_device_log(RDyHipOperator op, int32_t kind, const double **d_log) {
@@ -176,7 +147,7 @@ extern "C" int rdyhip_series_clear(RDyHipOperator op, int32_t kind) {
   int rc = series_check(op, kind, &s);
   if (!rc) rc = series_check_enabled(s, kind);
   if (rc) return rc;
-  s->times.clear();
+  series_clear(*s);
   return 0;
 }
 

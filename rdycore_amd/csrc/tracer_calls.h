@@ -9,18 +9,10 @@ using TracerKernelFn = void (*)(const KernelArgs, const TracerArgs, const double
 // The instantiation of the tracer kernel for (family: hydrostatic reconstruction (rdyhip_tracer_hr_enable) or plain, slots per
 // cell, number of tracers, upwind tracer flux): 2 x (2 x 7 x 2) = 56
 TracerKernelFn tracer_kernel_fn(bool hr, int S, int nt, bool upwind) {
-  return with_flag(S == 4, [&](auto quad) { return with_flag(upwind, [&](auto up) -> TracerKernelFn {
-    constexpr int s = quad ? 4 : 3;
-    switch (nt) {
-      case 1: return hr ? tracer_hr_kernel<s, 1, up> : tracer_rhs_kernel<s, 1, up>;
-      case 2: return hr ? tracer_hr_kernel<s, 2, up> : tracer_rhs_kernel<s, 2, up>;
-      case 3: return hr ? tracer_hr_kernel<s, 3, up> : tracer_rhs_kernel<s, 3, up>;
-      case 4: return hr ? tracer_hr_kernel<s, 4, up> : tracer_rhs_kernel<s, 4, up>;
-      case 5: return hr ? tracer_hr_kernel<s, 5, up> : tracer_rhs_kernel<s, 5, up>;
-      case 6: return hr ? tracer_hr_kernel<s, 6, up> : tracer_rhs_kernel<s, 6, up>;
-      default: return hr ? tracer_hr_kernel<s, 7, up> : tracer_rhs_kernel<s, 7, up>;
-    }
-  }); });
+  return with_flag(S == 4, [&](auto quad) { return with_flag(upwind, [&](auto up) { return with_tracer_count(nt, [&](auto n) -> TracerKernelFn {
+    constexpr int s = quad ? 4 : 3, t = decltype(n)::value;
+    return hr ? tracer_hr_kernel<s, t, up> : tracer_rhs_kernel<s, t, up>;
+  }); }); });
 }
 
 // null operator, tracers not enabled: what every call after rdyhip_tracers_enable starts with

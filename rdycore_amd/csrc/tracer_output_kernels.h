@@ -15,9 +15,9 @@
 //
 //   error sums, e = u[loc(o)][c] - exact[o][c] (exact == nullptr: e = u), c < N: the scheme of error_partial_kernel /
 //   error_finalize_kernel (readout_kernels.h) with records of 3 N + 1 values (l1[N], l2_squared[N], linf[N], area) instead of
-//   ten: the same block size, the same number of workgroups G for n_owned, the same lane-to-cell assignment, the same fold (a
-//   shuffle tree over the lanes of a wave, then the waves in order; in the second launch lane t takes records t, t + ERR_BLOCK,
-//   ...), and per component the same three operations.  Every order of addition depends on (n_owned, G) alone, so component c < 3
+//   ten: the same block size, the same number of workgroups G for n_owned, the same lane-to-cell assignment, the same fold
+//   (err_fold<N> / err_block_fold_store<N> of readout_kernels.h, taken with N = 3 there: a shuffle tree over the lanes of a
+//   wave, then the waves in order; in the second launch lane t takes records t, t + ERR_BLOCK, ...), and per component the same three operations.  Every order of addition depends on (n_owned, G) alone, so component c < 3
 //   comes out as the bits error_partial_kernel gives for the [cell][3] slice of the same state.  At most 31 sums per lane, all in
 //   registers.  (3 N + 1) * 8 bytes of LDS per wave, no scratch.
 //
@@ -89,39 +89,6 @@ __global__ void __launch_bounds__(TOUT_BLOCK) tracer_planes_kernel(int n_owned, 
   }
 }
 
-// values [2 N, 3 N) are maxima, the others sums
-template <int N>
-__device__ __forceinline__ double tracer_err_fold(int i, double a, double b) {
-  return (i >= 2 * N && i < 3 * N) ? fmax(a, b) : a + b;
-}
-
-// err_block_fold_store (readout_kernels.h) for a record of 3 N + 1 values
-template <int N>
-__device__ __forceinline__ void tracer_err_block_fold_store(double (&v)[3 * N + 1], double *__restrict__ record) {
-  constexpr int   V = 3 * N + 1;
-  __shared__ double waves[ERR_WAVES][V];
-#pragma unroll
-  for (int i = 0; i < V; ++i) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v[i] = tracer_err_fold<N>(i, v[i], __shfl_down(v[i], d, 64));
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < V; ++i) waves[wave][i] = v[i];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int i = 0; i < V; ++i) {
-      double r = waves[0][i];
-#pragma unroll
-      for (int w = 1; w < ERR_WAVES; ++w) r = tracer_err_fold<N>(i, r, waves[w][i]);
-      record[i] = r;
-    }
-  }
-}
-
 // records[blockIdx.x][3 N + 1]: the sums over the owned cells o = blockIdx.x * ERR_BLOCK + threadIdx.x + j * gridDim.x * ERR_BLOCK
 template <int NT>
 __global__ void __launch_bounds__(ERR_BLOCK) tracer_error_partial_kernel(int n_owned, const int32_t *__restrict__ o2l, const double *__restrict__ u,
@@ -151,7 +118,7 @@ __global__ void __launch_bounds__(ERR_BLOCK) tracer_error_partial_kernel(int n_o
     }
     v[3 * N] += a;
   }
-  tracer_err_block_fold_store<N>(v, records + (int64_t)blockIdx.x * V);
+  err_block_fold_store<N>(v, records + (int64_t)blockIdx.x * V);
 }
 
 // result[3 N + 1] = the fold of records[0 .. n_records); one workgroup
@@ -163,9 +130,9 @@ __global__ void __launch_bounds__(ERR_BLOCK) tracer_error_finalize_kernel(int n_
   for (int i = 0; i < V; ++i) v[i] = 0.0;
   for (int r = threadIdx.x; r < n_records; r += ERR_BLOCK) {
 #pragma unroll
-    for (int i = 0; i < V; ++i) v[i] = tracer_err_fold<N>(i, v[i], records[(int64_t)r * V + i]);
+    for (int i = 0; i < V; ++i) v[i] = err_fold<N>(i, v[i], records[(int64_t)r * V + i]);
   }
-  tracer_err_block_fold_store<N>(v, result);
+  err_block_fold_store<N>(v, result);
 }
 
 // One thread per owned cell.
